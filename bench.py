@@ -2,7 +2,8 @@
 """Benchmark: CogVideoX-5B + TTT-MLP training step (forward + backward + AdamW), BASELINE.json metric
 "DiT+TTT fwd/bwd video-tokens/sec".
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full   (+ sizing walk, fsdp1 comparison, legs, CPU baseline: under ten minutes)
     python bench.py --gpus N --steps K --warmup W          (no launcher: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -18,7 +19,8 @@ BASELINE configs[1] (adapter "sft", configs/train/ttt-mlp/3s.toml), 30sec / 63se
 
 MI355X-first memory policy (same arithmetic as the reference's settings, which remain available as flags):
   --remat-free-layers auto   leading layers that keep their activations instead of being re-materialised in backward,
-                             sized to the GPU's 288 GB with untimed probe steps (0 = the reference's 80-GB setting)
+                             sized to the GPU's 288 GB with untimed probe steps (0 = the reference's 80-GB setting); where
+                             that walk's end is committed (SIZED_FREE_LAYERS) a run without --full starts there
   (default)                  FSDP keeps the gathered bf16 parameters resident (--reshard-after-forward = reference)
   (default)                  committed hipBLASLt / rocBLAS solution selections for this model's GEMM shapes (--no-tuned-gemms)
 
@@ -27,10 +29,10 @@ Rank 0 prints ONE JSON line.  Besides the driver contract it carries
                  events around every launch on the launch stream); `traffic` = HBM bytes per launch from the committed PMC
                  passes of the same kernel build at the same scan length (profiles/*pmc_traffic*.json, `traffic_source`), null
                  when none matches; the other hand-written kernels are listed under roofline.other
-  cpu_baseline - N=1 only: the CPU port of the same layer (fp32, eager; the TTT scan = the oracle's restatement of the
+  cpu_baseline - N=1, --full only: the CPU port of the same layer (fp32, eager; the TTT scan = the oracle's restatement of the
                  reference ops path, dual form with the reference's checkpoint groups) timed on the host cores on a bounded
                  sample
-  fsdp1        - N=1 only: the same step through FSDP2 over a one-rank mesh (the code path of N > 1), a few timed steps, so
+  fsdp1        - N=1, --full only: the same step through FSDP2 over a one-rank mesh (the code path of N > 1), a few timed steps, so
                  that a 1 -> 8 curve can be read like for like
 """
 import argparse
@@ -73,7 +75,7 @@ def parse():
                          "TTT projections, TTT inner parameters and gates only (its longer stages, 9s.toml ...); auto = the reference's "
                          "setting for the chosen --video-length")
     ap.add_argument("--no-fsdp1-compare", action="store_true",
-                    help="N=1: skip the extra short run through FSDP2 over a one-rank mesh (reported as `fsdp1`)")
+                    help="--full, N=1: skip the extra short run through FSDP2 over a one-rank mesh (reported as `fsdp1`)")
     ap.add_argument("--fsdp1-steps", type=int, default=3)
     ap.add_argument("--cpu-baseline-budget", type=float, default=25.0, help="seconds of CPU work the cpu_baseline sample is sized for")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -131,13 +133,21 @@ def parse():
     ap.add_argument("--role", default=None, choices=["orchestrate", "worker"],
                     help="worker = a measuring process (one per GPU; what a launcher starts).  orchestrate (the default WITHOUT a launcher "
                          "environment) = a thin parent that holds no GPU context: it starts the measurement as child process(es) - under "
-                         "torch.distributed.run for --gpus N > 1 -, retries ONCE with conservative memory settings if that fails, then (N = 1, "
+                         "torch.distributed.run for --gpus N > 1 -, retries ONCE with conservative memory settings if that fails, then (--full, N = 1, "
                          "default workload) runs the metric's other contexts as legs `ctx3s` / `ctx63s` and the CPU baseline, and prints the ONE JSON line")
-    ap.add_argument("--no-legs", action="store_true", help="N=1: skip the legs (`ctx3s` = BASELINE configs[1], `ctx63s` = the metric's 63 s context, `ctx30s` = configs[3], `sample63s` = configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline measurement: the sizing walk of --remat-free-layers auto (probe steps) on every workload, the "
+                         "fsdp1 comparison run, the legs and the CPU baseline (N=1).  Without it a run sets up, warms up, times --steps steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/*.npy: the loss, and a fixed seeded sample of the "
+                         "gradients and of the updated parameters the optimizer holds (float32 / float64, 16 MiB in all)")
+    ap.add_argument("--no-legs", action="store_true", help="--full, N=1: skip the legs (`ctx3s` = BASELINE configs[1], `ctx63s` = the metric's 63 s context, `ctx30s` = configs[3], `sample63s` = configs[4])")
     ap.add_argument("--leg-steps", type=int, default=2, help="timed steps of each leg (after one warm-up step)")
-    ap.add_argument("--legs", default="all", help="N=1: which legs run after the main measurement: 'all' or a comma list of ctx3s, ctx63s, ctx30s, sample63s")
-    ap.add_argument("--time-budget", type=float, default=1500.0,
-                    help="seconds the whole default run may take: a leg whose estimated duration does not fit is skipped with a stated reason")
+    ap.add_argument("--legs", default="all", help="--full, N=1: which legs run after the main measurement: 'all' or a comma list of ctx3s, ctx63s, ctx30s, sample63s")
+    ap.add_argument("--time-budget", type=float, default=480.0,
+                    help="--full: seconds the measurement and the legs may take together (the CPU baseline follows): a leg whose estimated "
+                         "duration does not fit is skipped with a stated reason, one that overruns what is left is stopped")
     ap.add_argument("--retry-reason", default=None, help=argparse.SUPPRESS)          # set by the orchestrator on its second attempt
     ap.add_argument("--pipeline-parts", type=int, default=None,
                     help="TTT-MLP layer forward as a pipeline over this many parts of the sequence (the scan of one part on a side stream beside "
@@ -385,11 +395,13 @@ def cpu_baseline(ssm_layer, budget_s=25.0):
                       f"value / {ratio} = `value_at_full_segment`"}
 
 
-def size_warm_and_time(step, hk, remat_free_layers, warmup, steps, world):
+def size_warm_and_time(step, hk, remat_free_layers, warmup, steps, world, sized=None):
     """Activation re-materialisation sized for this GPU, warm-up and the timed region - the control flow every rank of an
     N-GPU run must walk IDENTICALLY (a rank that takes another branch leaves the others in a collective).  `hk` supplies the
     device: memory statistics, synchronisation, the MIN all-reduce, barriers (tests/test_bench_policy_gloo.py drives this
     function on two gloo ranks with a fake device).  Returns (remat_free_layers used, seconds of the timed region, last loss).
+    `sized` (automatic setting only): where the sizing walk is known to end for this run (sized_free_layers()) - the probe
+    steps and refinements are skipped, an out-of-memory error or allocator retries still back off.
 
     The reference checkpoints every transformer layer (configs/train/ttt-mlp/3s.toml:31, tuned for 80 GB GPUs).  With 288 GB
     per MI355X most layers can keep their activations: probe the per-layer activation footprint with two untimed steps and
@@ -399,7 +411,9 @@ def size_warm_and_time(step, hk, remat_free_layers, warmup, steps, world):
     cap = 0.88 if world == 1 else 0.80
     auto = remat_free_layers == "auto"
     peak0 = 0
-    if auto:
+    if auto and sized is not None:
+        n_free = sized
+    elif auto:
         # layers in the second probe step: 4 at the 3 s geometry (2.7 GB of activations per layer and sample), 1 for the long
         # videos, whose layers are 3 - 20 x larger; an out-of-memory error in the probe means "none fit"
         probe = hk.probe_layers
@@ -460,7 +474,7 @@ def size_warm_and_time(step, hk, remat_free_layers, warmup, steps, world):
             ok = 0
         if world > 1:
             ok = hk.all_reduce_min(ok)
-        if ok and auto and refinements < 3 and 0 < n_free < hk.num_layers:
+        if ok and auto and sized is None and refinements < 3 and 0 < n_free < hk.num_layers:
             # up to two free refinements with the footprint measured at the chosen setting (the walk at 9 s was 3 -> 8 -> 13; a third
             # refinement finds room for a 14th layer and buys nothing measurable: 8 139 / 8 114 against 8 155 / 8 104 video-tok/s on
             # one box at 243 instead of 237 GiB, profiles/r5h_*; the probe over-estimates a layer's
@@ -524,6 +538,52 @@ def size_warm_and_time(step, hk, remat_free_layers, warmup, steps, world):
             n_free = back_off()
             continue
         return n_free, dt, loss
+
+
+# Where the sizing walk of --remat-free-layers auto ends for the default workload on the replica path of ONE 288-GB MI355X: 3 -> 8 -> 13 -> 14
+# layers in every default run of round 6 (profiles/r6zz_bench_default.err).  A run without --full starts there instead of walking (the
+# probe steps and refinements cost several steps before the warm-up); --full walks, so its line shows whether the entry still holds.
+SIZED_FREE_LAYERS = {("9sec", "ttt_mlp"): 14}
+SIZED_DEVICE_GIB = 288
+
+
+def sized_free_layers(args, world, replica, total_memory):
+    """SIZED_FREE_LAYERS' entry for this run, or None: --full, another workload, device or memory setting (anything that changes
+    the activation footprint: re-materialisation and offload options, batch, layers, parallelism, kernels, GEMM selections)"""
+    if args.full or args.remat_free_layers != "auto" or world != 1 or not replica or args.tp or abs(total_memory / 2 ** 30 - SIZED_DEVICE_GIB) > 8:
+        return None
+    if (args.layers is not None or args.local_batch != 1 or args.adapter != "qkvo" or args.remat_keep != "attn,scan,fc2"
+            or args.remat_keep_layers is not None or args.offload_gib_per_layer > 0 or args.offload_park_kept or args.pipeline_parts is not None
+            or args.debug_option or args.impl != "auto" or args.no_tuned_gemms):
+        return None
+    return SIZED_FREE_LAYERS.get((args.video_length, args.ssm_layer))
+
+
+DUMP_SAMPLE = 1 << 21        # values per sampled array: 2 x 8 MiB of float32
+
+
+def dump_outputs(out_dir, loss, params, seed=0):
+    """What a caller of the timed step receives, after its last step: `loss.npy` (float64), and of the trained parameters (the
+    optimizer's, in its order) `grads_sample.npy` / `params_sample.npy` - float32 values of the gradients of that step (as the
+    optimizer used them: clipped) and of the updated parameters at DUMP_SAMPLE positions drawn with a fixed seed over all of them
+    end to end, sorted.  Same arguments -> same positions, so two builds compare value for value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.detach())], dtype=np.float64))
+    local = lambda t: t.to_local() if hasattr(t, "to_local") else t          # (FSDP2: DTensor shards; this rank's part)
+    sizes = torch.tensor([local(p).numel() for p in params], dtype=torch.int64)
+    ends = sizes.cumsum(0)
+    pos = torch.randint(int(ends[-1]), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed), dtype=torch.int64).sort().values
+    owner = torch.searchsorted(ends, pos, right=True)
+    grads, vals = [], []
+    for i in owner.unique().tolist():
+        p = local(params[i].detach())
+        at = (pos[owner == i] - (ends[i] - sizes[i])).to(p.device)
+        vals.append(p.reshape(-1)[at].float().cpu())
+        g = params[i].grad
+        grads.append(local(g.detach()).reshape(-1)[at].float().cpu() if g is not None else torch.full((len(at),), float("nan")))
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(grads).numpy())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(vals).numpy())
 
 
 def launcher_argv(gpus, argv, port=None):
@@ -654,9 +714,10 @@ def rccl_summary(log_dir):
 # the setting of rounds 5 / 6 and the leg's fallback if the parked attempt fails).
 CTX63S_KEEP = ["--remat-keep", "attn", "--offload-park-kept", "--offload-lookahead", "2"]
 CTX63S_KEEP_FALLBACK = ["--remat-keep", "attn", "--remat-keep-layers", "10"]
-# generous estimates (model build + sizing probes + 1 warm-up + 2 timed steps; 24 s per step at 30 s, 49 s at 63 s; sampling: two
-# network evaluations of 22 s on the guidance pair + the build)
-LEG_ESTIMATE_S = {"ctx3s": 150.0, "ctx63s": 480.0, "ctx30s": 380.0, "sample63s": 240.0}
+# estimates with a margin (model build + sizing probes + 1 warm-up + 2 timed steps; 24 s per step at 30 s, 49 s at 63 s; sampling: two
+# network evaluations of 22 s on the guidance pair + the build); measured: 26, 194, 127 and 76 s (profiles/r6zz_bench_default.err).
+# A --full run stays inside ten minutes: --time-budget for the measurement and the legs, then the CPU baseline (~80 s)
+LEG_ESTIMATE_S = {"ctx3s": 60.0, "ctx63s": 270.0, "ctx30s": 180.0, "sample63s": 120.0}
 LEG_ORDER = ("ctx3s", "ctx63s", "ctx30s", "sample63s")     # the metric's two contexts first, then BASELINE configs[3] and configs[4]
 
 
@@ -741,7 +802,7 @@ def orchestrate(args, argv):
         if attempt:
             extra = extra + ["--retry-reason", failures[-1][:300]]
             log(f"measurement failed ({failures[-1][:200]}): retrying ONCE with {' '.join(SAFE_MEMORY_ARGS)}")
-        rc, line, tail = run_child(worker_command(args.gpus, argv + extra), timeout=max(600.0, args.time_budget), env=env)
+        rc, line, tail = run_child(worker_command(args.gpus, argv + extra), timeout=max(1500.0, args.time_budget), env=env)
         if rc == 0 and line is not None:
             break
         why = next((t for t in reversed(tail) if "OutOfMemory" in t or "out of memory" in t), None) or \
@@ -760,7 +821,7 @@ def orchestrate(args, argv):
         for k in ("value", "ms_per_step"):
             if isinstance(line["fsdp1"].get(k), (int, float)):
                 line["config"][f"fsdp1_{k}"] = line["fsdp1"][k]
-    if args.gpus == 1 and not args.no_legs and default_workload:
+    if args.full and args.gpus == 1 and not args.no_legs and default_workload:
         wanted = [n for n in LEG_ORDER if args.legs == "all" or n in args.legs.split(",")]
         for name in wanted:
             left = args.time_budget - (time.time() - t_start)
@@ -775,13 +836,13 @@ def orchestrate(args, argv):
             short = room is not None and room < CTX63S_PARKED_HOST_GIB
             if short:
                 log(f"{name}: {room:.0f} GiB of host memory to spare (< {CTX63S_PARKED_HOST_GIB:.0f}): attention outputs of ten layers on the device instead of parked")
-            rc, leg, tail = run_child(leg_command(name, args, fallback=short), timeout=max(300.0, left))
+            rc, leg, tail = run_child(leg_command(name, args, fallback=short), timeout=left)
             fell_back = f"host memory: {room:.0f} GiB to spare" if short else None
             if name == "ctx63s" and not short and not (rc == 0 and leg is not None) and args.time_budget - (time.time() - t_start) >= LEG_ESTIMATE_S[name]:
                 # the parked attempt failed: once more with the attention outputs of ten layers kept on the device (rounds 5 / 6)
                 fell_back = f"rc {rc}: {(tail[-1] if tail else 'no output')[:200]}"
                 log(f"{name}: parked attempt failed ({fell_back}); once more with {' '.join(CTX63S_KEEP_FALLBACK)}")
-                rc, leg, tail = run_child(leg_command(name, args, fallback=True), timeout=max(300.0, args.time_budget - (time.time() - t_start)))
+                rc, leg, tail = run_child(leg_command(name, args, fallback=True), timeout=args.time_budget - (time.time() - t_start))
             if rc == 0 and leg is not None:
                 res = leg_summary(leg)
                 res["leg_wall_s"] = round(time.time() - t0, 1)
@@ -790,7 +851,7 @@ def orchestrate(args, argv):
             else:
                 res = {"error": f"rc {rc}: {(tail[-1] if tail else 'no output')[:300]}"}
             attach_leg(line, name, res)
-    if args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and args.gpus == 1 and not args.no_cpu_baseline:
         # the CPU leg runs in a child process with a wall-clock limit: whatever happens to it (host out-of-memory kill, a slow
         # box) the GPU measurement above is still printed
         log("cpu_baseline leg (child process)")
@@ -853,7 +914,7 @@ def main():
         torch.cuda.empty_cache()
         if line is None:
             line = _run(args, world, rank, local_rank, dev, no_fsdp=False, sharded=multi)
-        elif not args.no_fsdp1_compare and mode == "auto":
+        elif args.full and not args.no_fsdp1_compare and mode == "auto":
             # the same step through the sharded path over a one-rank group WITH its collectives (RCCL all-gather / reduce-scatter
             # of one rank) = the code path of N > 1 (like-for-like point of a 1 -> N curve)
             try:
@@ -1085,7 +1146,12 @@ def _run(args, world, rank, local_rank, dev, no_fsdp, quiet=False, tp=False, sha
             if clocks:
                 clocks.stop()
 
-    n_free, dt, loss = size_warm_and_time(step, Hooks, args.remat_free_layers, args.warmup, args.steps, world)
+    sized = sized_free_layers(args, world, replica is not None, Hooks.total_memory)
+    if sized is not None and rank == 0:
+        log(f"sizing: remat_free_layers={sized}, where the sizing walk ends for this workload on this device (--full walks)")
+    n_free, dt, loss = size_warm_and_time(step, Hooks, args.remat_free_layers, args.warmup, args.steps, world, sized=sized)
+    if args.dump_outputs and rank == 0 and not quiet:
+        dump_outputs(args.dump_outputs, loss, train_params)
     fast0 = fast0[0]
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1177,7 +1243,7 @@ def _run(args, world, rank, local_rank, dev, no_fsdp, quiet=False, tp=False, sha
                 "config": {"workload": f"CogVideoX-5B+{args.ssm_layer} {args.video_length} training step (fwd+bwd+AdamW), "
                                        f"{cfg.num_layers} layers, L={L} tokens/sample, adapter={args.adapter}",
                            "global_batch": dp * LB, "seq_len": L, "parallelism": (f"tp{tp}" if no_fsdp else f"fsdp{world}(dp{dp}xtp{tp})") if tp else ("replica1" if no_fsdp else (f"flat_fsdp{world}" if (communicate or world > 1) else "flat1") if flat else f"fsdp2_{world}"), "ttt_impl": args.impl,
-                           "remat_free_layers": n_free, "remat_keep": list(dit.remat_keep), "remat_keep_layers": args.remat_keep_layers, "remat_keep_limits": dict(dit.remat_keep_limits) or None, "ttt_pipeline_parts": parts_used, "fsdp_reshard_after_forward": bool(args.reshard_after_forward), "tuned_gemm_selections": bool(tuned),
+                           "remat_free_layers": n_free, "remat_free_sizing": "fixed" if args.remat_free_layers != "auto" else ("walk" if sized is None else "committed"), "remat_keep": list(dit.remat_keep), "remat_keep_layers": args.remat_keep_layers, "remat_keep_limits": dict(dit.remat_keep_limits) or None, "ttt_pipeline_parts": parts_used, "fsdp_reshard_after_forward": bool(args.reshard_after_forward), "tuned_gemm_selections": bool(tuned),
                            "debug_options": ",".join(args.debug_option) or None,
                            "host_offload": ({"gib_per_layer": args.offload_gib_per_layer, "layers": args.offload_layers, "park_kept": args.offload_park_kept,
                                              "gib_per_step": round(offload.stats["offloaded_bytes"] / args.steps / 2 ** 30, 2),

@@ -173,7 +173,7 @@ def test_failed_multi_gpu_attempt_is_retried_once_with_safe_memory_settings(monk
 
 
 def test_one_gpu_default_run_carries_the_other_contexts_as_legs(monkeypatch, capsys):
-    """N = 1, default workload: after the 9 s measurement the parent runs BASELINE configs[1] (3 s), the metric's second context
+    """N = 1, default workload, --full: after the 9 s measurement the parent runs BASELINE configs[1] (3 s), the metric's second context
     (63 s), configs[3] (the 30 s stage) and configs[4] (one 63 s denoising step) as legs - own processes - and the CPU baseline, and
     merges them into the ONE line where the driver's record keeps them: `config.legs` + flat `config.leg_*` scalars (round 5: the
     driver kept only the NAMES of other top-level keys); a leg that does not fit the time budget is skipped with a stated reason; a
@@ -186,7 +186,7 @@ def test_one_gpu_default_run_carries_the_other_contexts_as_legs(monkeypatch, cap
             "projected_50_step_video_s": 1090.0, "peak_mem_GiB": 101.0,
             "config": {"workload": "sampling 63sec", "layers": 42, "timed_steps": 1, "tokens": 351168, "mini_batches": 21948, "scan_impl": "mfma"}}
     main_line = dict(_LINE, fsdp1={"impl": "flat", "value": 6990.0, "ms_per_step": 7100.0})
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "2"],
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "2", "--full"],
                                   [(0, main_line, []), (0, leg3, []), (0, leg63, []), (0, leg30, []), (0, samp, []), (0, {"cpu_baseline": {"value": 1.2}}, [])])
     assert rc == 0 and len(out) == 1 and len(calls) == 6
     line = out[0]
@@ -210,29 +210,92 @@ def test_one_gpu_default_run_carries_the_other_contexts_as_legs(monkeypatch, cap
     assert "--no-fsdp1-compare" in c3 and c3[-2:] == ["--role", "worker"] and "--remat-free-layers" not in c30
     assert cs[1].endswith(os.path.join("tools", "sample_bench.py")) and cs[cs.index("--video-length") + 1] == "63sec" and cs[cs.index("--steps") + 1] == "1"
     # a subset of the legs
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--legs", "ctx3s,sample63s", "--no-cpu-baseline"], [(0, _LINE, []), (0, leg3, []), (0, samp, [])])
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--legs", "ctx3s,sample63s", "--no-cpu-baseline"], [(0, _LINE, []), (0, leg3, []), (0, samp, [])])
     assert rc == 0 and len(calls) == 3 and list(out[0]["config"]["legs"]) == ["ctx3s", "sample63s"]
     # no time left: every leg skipped with a reason, the main line and the CPU baseline still there
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--time-budget", "100"], [(0, _LINE, []), (0, {"cpu_baseline": {"value": 1.2}}, [])])
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--time-budget", "50"], [(0, _LINE, []), (0, {"cpu_baseline": {"value": 1.2}}, [])])
     assert rc == 0 and len(calls) == 2 and all("budget" in out[0]["config"]["legs"][n]["skipped"] for n in bench.LEG_ORDER)
     assert "budget" in out[0]["config"]["leg_ctx30s_skipped"]
     # a leg that dies: its entry says so
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--no-cpu-baseline", "--legs", "ctx3s,ctx63s"], [(0, _LINE, []), (1, None, ["HIP error"]), (0, leg63, [])])
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--no-cpu-baseline", "--legs", "ctx3s,ctx63s"], [(0, _LINE, []), (1, None, ["HIP error"]), (0, leg63, [])])
     assert rc == 0 and "error" in out[0]["config"]["legs"]["ctx3s"] and out[0]["config"]["legs"]["ctx63s"]["value"] == 6400.0
     assert "HIP error" in out[0]["config"]["leg_ctx3s_error"]
     # the parked 63 s attempt dies: once more with the attention outputs of ten layers on the device, and the entry says why
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--no-cpu-baseline", "--legs", "ctx63s"], [(0, _LINE, []), (1, None, ["HIP out of memory"]), (0, leg63, [])])
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--no-cpu-baseline", "--legs", "ctx63s"], [(0, _LINE, []), (1, None, ["HIP out of memory"]), (0, leg63, [])])
     fb = calls[2][0]
     assert rc == 0 and len(calls) == 3 and fb[fb.index("--remat-keep-layers") + 1] == "10" and "--offload-park-kept" not in fb
     assert out[0]["config"]["legs"]["ctx63s"]["value"] == 6400.0 and "out of memory" in out[0]["config"]["legs"]["ctx63s"]["fallback_after"]
     # a box without 160 GiB of host memory to spare: the parked attempt is not made at all
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--no-cpu-baseline", "--legs", "ctx63s"], [(0, _LINE, []), (0, leg63, [])], host_gib=62.0)
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--no-cpu-baseline", "--legs", "ctx63s"], [(0, _LINE, []), (0, leg63, [])], host_gib=62.0)
     only = calls[1][0]
     assert rc == 0 and len(calls) == 2 and "--offload-park-kept" not in only and only[only.index("--remat-keep-layers") + 1] == "10"
     assert "62 GiB" in out[0]["config"]["legs"]["ctx63s"]["fallback_after"]
     # another workload than the metric's: no legs
-    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--video-length", "3sec", "--no-cpu-baseline"], [(0, _LINE, [])])
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--full", "--video-length", "3sec", "--no-cpu-baseline"], [(0, _LINE, [])])
     assert len(calls) == 1 and "ctx3s" not in out[0] and "legs" not in out[0]["config"]
+
+
+def test_plain_one_gpu_run_is_the_measurement_alone(monkeypatch, capsys):
+    """Without --full the one-GPU default run starts ONE child - the measurement, its arguments handed through (--dump-outputs
+    included) - and prints its line: no legs, no CPU baseline (the fsdp1 comparison and the sizing walk are the worker's, --full too)."""
+    import bench
+    calls, out, rc = _orchestrate(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d"], [(0, _LINE, [])])
+    assert rc == 0 and len(calls) == 1 and len(out) == 1
+    assert calls[0][0][1:] == [os.path.abspath(bench.__file__), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d", "--role", "worker"]
+    line = out[0]
+    assert line["value"] == 7000.0 and line["ms_per_step"] == 7000.0 and line["steps"] == 7
+    assert "legs" not in line["config"] and "ctx3s" not in line and "cpu_baseline" not in line
+
+
+def test_committed_sizing_applies_to_the_plain_default_run_only(monkeypatch):
+    """bench.sized_free_layers: the committed end of the sizing walk is used by a run without --full of the default workload on
+    the replica path of a 288-GB device, and by nothing else."""
+    import bench
+    GiB = 1 << 30
+
+    def args(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", *argv])
+        a = bench.parse()
+        if a.adapter == "auto":                                   # (as bench.main resolves it)
+            a.adapter = "sft" if a.video_length == "3sec" else "qkvo"
+        return a
+
+    assert bench.sized_free_layers(args(), 1, True, 288 * GiB) == bench.SIZED_FREE_LAYERS[("9sec", "ttt_mlp")] == 14
+    assert bench.sized_free_layers(args("--steps", "9", "--warmup", "0", "--dump-outputs", "d"), 1, True, 287.6 * GiB) == 14
+    for argv in (["--full"], ["--video-length", "3sec"], ["--ssm-layer", "ttt_linear"], ["--remat-free-layers", "13"], ["--layers", "4"],
+                 ["--remat-keep", "attn"], ["--remat-keep-layers", "3"], ["--offload-gib-per-layer", "2"], ["--offload-park-kept"],
+                 ["--local-batch", "2"], ["--adapter", "sft"], ["--pipeline-parts", "2"], ["--impl", "mfma"], ["--no-tuned-gemms"],
+                 ["--debug-option", "tail5=0"], ["--tp", "1"]):
+        assert bench.sized_free_layers(args(*argv), 1, True, 288 * GiB) is None, argv
+    assert bench.sized_free_layers(args(), 2, True, 288 * GiB) is None           # several ranks
+    assert bench.sized_free_layers(args(), 1, False, 288 * GiB) is None          # a sharded holder
+    assert bench.sized_free_layers(args(), 1, True, 192 * GiB) is None           # another device
+
+
+def test_dump_outputs_writes_a_fixed_seeded_sample(tmp_path):
+    """bench.dump_outputs: loss (float64) and the gradients / parameters at fixed seeded positions over all trained parameters
+    end to end (float32), the same positions on every call, under 64 MiB in all."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    ps = [torch.nn.Parameter(torch.randn(n, generator=g)) for n in (5, 1000, 0, 300000)]
+    ps[1] = torch.nn.Parameter(ps[1].detach().reshape(10, 100))
+    for p in ps:
+        p.grad = torch.randn(p.shape, generator=g)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.25), ps)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads_sample.npy", "loss.npy", "params_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        np.testing.assert_array_equal(a[f], np.load(tmp_path / "b" / f))
+    assert a["loss.npy"].dtype == np.float64 and a["loss.npy"].tolist() == [1.25]
+    pos = torch.randint(301005, (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    for f, flat in (("params_sample.npy", torch.cat([p.detach().reshape(-1) for p in ps])), ("grads_sample.npy", torch.cat([p.grad.reshape(-1) for p in ps]))):
+        assert a[f].dtype == np.float32 and a[f].shape == (bench.DUMP_SAMPLE,)
+        np.testing.assert_array_equal(a[f], flat[pos].numpy())
 
 
 def test_run_child_kills_the_whole_process_group_on_timeout(tmp_path):

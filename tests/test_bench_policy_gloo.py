@@ -177,3 +177,24 @@ def test_timed_region_oom_on_a_multi_rank_run_is_fatal_on_that_rank():
     hk = Solo(2, 288 * GB, 60 * GB, 5 * GB, timed_oom_at=34)
     with pytest.raises(FakeOOM):
         bench.size_warm_and_time(hk.step, hk, "auto", 1, 2, 2)
+
+
+def test_committed_sizing_skips_the_walk_and_still_backs_off():
+    """`sized` (bench.sized_free_layers: a run without --full of a workload whose walk is committed): no probe steps, no
+    refinements - the warm-up starts at that setting; an out-of-memory error there backs off as on the walk."""
+    import bench
+    GB = 1 << 30
+    hk = FakeDevice(1, 288 * GB, 60 * GB, 5 * GB)
+    steps = []
+
+    def step():
+        steps.append(hk.n_free)
+        return hk.step()
+    n, dt, loss = bench.size_warm_and_time(step, hk, "auto", 2, 3, 1, sized=30)
+    assert n == 30 and steps == [30] * 5 and hk.timed_regions == 1
+    hk = FakeDevice(1, 288 * GB, 60 * GB, 5 * GB, warm_oom_at=30)
+    n, dt, loss = bench.size_warm_and_time(hk.step, hk, "auto", 1, 3, 1, sized=30)
+    assert n == 27 and hk.timed_regions == 1 and hk.log.count("release") == 1
+    hk = FakeDevice(1, 288 * GB, 60 * GB, 5 * GB)                       # an explicit setting wins
+    n, dt, loss = bench.size_warm_and_time(hk.step, hk, "12", 1, 3, 1, sized=30)
+    assert n == 12

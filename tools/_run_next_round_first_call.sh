@@ -5,7 +5,7 @@ cd /root/repo; mkdir -p gpurun_out/next; O=gpurun_out/next
 # 1. the full device suite on the final tree (146 collected; the last file holds the host-offload test with the shipped defaults, never run on a device)
 timeout 1500 python -m pytest tests -x -q -m gpu > $O/gpu_suite.log 2>&1; tail -3 $O/gpu_suite.log
 # 2. the driver's command (the 63 s leg now parks the attention outputs of all 42 layers: expect ~43 s/step; `fallback_after` in its entry says if it did not)
-timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; tail -c 3000 $O/bench_default.json
+timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 --full --time-budget 1500 > $O/bench_default.json 2> $O/bench_default.err; tail -c 3000 $O/bench_default.json
 # 3. the 63 s step with scan outputs parked too, inside the pinned cap (160 GiB: attention 92 GiB + 8 layers' scan outputs); same box: compare with the leg of (2)
 show() { grep -h "^{" $1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); c=d['config']; h=c.get('host_offload') or {}; print('$2', round(d['value'],1), 'ms', round(d['ms_per_step'],1), 'free', c['remat_free_layers'], c['remat_keep'], c.get('remat_keep_limits'), 'gib', h.get('gib_per_step'), 'pinned', h.get('pinned_gib'), 'peak', round(d['peak_mem_gib'],1))" || tail -3 ${1%.json}.err; }
 timeout 900 python bench.py --role worker --gpus 1 --video-length 63sec --steps 2 --warmup 1 --no-fsdp1-compare --remat-free-layers 0 --remat-keep attn,scan:8 --offload-park-kept --offload-lookahead 1 > $O/bench63_scan8.json 2> $O/bench63_scan8.err; show $O/bench63_scan8.json 63scan8

@@ -5,7 +5,7 @@ cd /root/repo; mkdir -p gpurun_out/r5f; O=$GRAFT_REPO_ROOT/gpurun_out/r5f
 export TMPDIR=/tmp
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -3 $O/smoke.log
 timeout 700 python -m pytest tests -x -q -m gpu > $O/gpu_suite.log 2>&1; echo "suite rc=$?"; tail -3 $O/gpu_suite.log
-timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 --full --time-budget 1500 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 grep -h "^{" $O/bench_default.json | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']
 print('value', round(d['value'],1), 'ms', round(d['ms_per_step'],1), 'free', d['config']['remat_free_layers'], 'frac', round(r['frac'],4), 'bwd ms', round(r['avg_launch_ms'],3), {k: round(v['avg_ms'],3) for k,v in r['other'].items()})

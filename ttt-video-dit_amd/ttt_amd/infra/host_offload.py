@@ -26,6 +26,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import time
+import weakref
 
 import torch
 
@@ -53,11 +54,11 @@ def host_room_gib():
 
 class _Stor:
     """One offloaded storage of one step."""
-    __slots__ = ("layer", "nbytes", "slot", "dev", "d2h_done", "restored", "h2d_done", "device", "queued")
+    __slots__ = ("layer", "nbytes", "slot", "dev", "d2h_done", "restored", "h2d_done", "device", "queued", "storage")
 
     def __init__(self, layer, nbytes, slot, dev, device):
         self.layer, self.nbytes, self.slot, self.dev, self.device = layer, nbytes, slot, dev, device
-        self.d2h_done = self.restored = self.h2d_done = None
+        self.d2h_done = self.restored = self.h2d_done = self.storage = None
         self.queued = False                           # batch mode: the copy out has not been issued yet
 
 
@@ -108,7 +109,7 @@ class HostOffload:
     # ---- per-step state ------------------------------------------------------------------------------------------------------
     def _new_step(self):
         self._by_layer: dict[int, list[_Stor]] = collections.defaultdict(list)
-        self._by_ptr: dict[int, _Stor] = {}           # device data_ptr of a storage that is offloaded in this step (while it is alive)
+        self._by_ptr: dict[int, _Stor] = {}           # device data_ptr of a storage that is offloaded in this step (valid while _Stor.storage lives)
         self._pending: collections.deque[_Stor] = collections.deque()     # copies out whose device copy is still held
         self._next_slot = 0
         self._spent = 0
@@ -218,7 +219,9 @@ class HostOffload:
         storage = t.untyped_storage()
         ptr, nbytes = storage.data_ptr(), storage.nbytes()
         hit = self._by_ptr.get(ptr)
-        if hit is not None and hit.nbytes == nbytes:                  # another view of a storage that already travels
+        # another view of a storage that already travels: the same storage object, alive - whether or not its device copy has been let go
+        # yet (that depends on when the copy out completes; the slots a step fills must not), and not an address handed out again
+        if hit is not None and hit.nbytes == nbytes and hit.storage() is storage:
             self.stats["views_shared"] += 1
             return _View(hit, t)
         if nbytes > self.max_storage_ratio * nbytes_view or self._spent + nbytes > self.bytes_per_layer:
@@ -227,8 +230,8 @@ class HostOffload:
         if stor is None:
             return t
         self._spent += nbytes
-        if stor.dev is not None:                                      # (a throttled copy may be complete, and its device copy let go, already)
-            self._by_ptr[ptr] = stor
+        stor.storage = weakref.ref(storage)
+        self._by_ptr[ptr] = stor
         return _View(stor, t)
 
     def _send(self, layer, t) -> _Stor | None:
@@ -304,7 +307,6 @@ class HostOffload:
 
     def _drop_dev(self, s):
         if s.dev is not None and s.restored is None:
-            self._by_ptr.pop(s.dev.untyped_storage().data_ptr(), None)   # (the address may be handed out again)
             s.dev = None
 
     def _backlog(self):

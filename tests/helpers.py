@@ -31,6 +31,71 @@ def max_abs(a, b):
     return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
 
 
+def row_rel_err(a, b, row_dims):
+    """Worst rel-L2 over rows: ``row_dims`` are the dims that index a row (e.g. (0, 1, 2) of [B, L, NH, F]: one (batch, token,
+    head)); the rest make up the row.  A tensor-wide rel-L2 hides one wrong token: at 18 048 tokens an entirely wrong token adds
+    about 7e-3.  Rows whose reference is zero count their absolute error."""
+    a = a.detach().double().cpu(); b = b.detach().double().cpu()
+    rest = [d for d in range(b.dim()) if d not in row_dims]
+    perm = list(row_dims) + rest
+    n = 1
+    for d in row_dims:
+        n *= b.shape[d]
+    diff = (a - b).permute(perm).reshape(n, -1).norm(dim=1)
+    ref = b.permute(perm).reshape(n, -1).norm(dim=1)
+    return float((diff / ref.clamp_min(1e-30)).where(ref > 0, diff).max())
+
+
+def bf16_ulp(x):
+    """spacing of bf16 numbers at |x| (x fp64): 2^(e - 7) for |x| in [2^e, 2^(e+1))"""
+    return torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(1e-38))) - 7)
+
+
+def ulp_stats(a, b64, floor=None):
+    """(fraction of elements more than 1 bf16 ulp from the fp64 reference, largest distance in bf16 ulps).  The ulp is taken at
+    max(|b|, floor): ``floor`` (default 1/8 of the reference's RMS) keeps results of cancellation near zero from counting
+    thousands of ulps for an absolute error at the level of the row's own rounding."""
+    a = a.detach().double().cpu(); b = b64.detach().double().cpu()
+    if floor is None:
+        floor = 0.125 * float(b.square().mean().sqrt())
+    u = bf16_ulp(b.abs().clamp_min(floor))
+    d = (a - b).abs() / u
+    return float((d > 1.0).double().mean()), float(d.max())
+
+
+# Tolerances of the glue kernels against oracle/glue_oracle.py (tests/test_prepost_oracle_gpu.py), fixed by the sensitivity table
+# of tests/test_glue_oracle_cpu.py: each sits >= 10x above the oracle's own fp32-vs-fp64 distance and >= 10x below the nearest
+# mutation it must catch.
+GLUE_TOL = {
+    "ulp_frac": 1e-3,     # fraction of bf16 outputs more than 1 ulp from fp64
+    "ulp_max": 64.0,      # largest distance in ulps (floor: 1/8 of the reference's RMS): one wild element
+    "row": 2e-2,          # worst rel-L2 of one (batch, token, head) / (batch, token) row against the bf16-rounded reference
+    "psum": 1e-4,         # rel-L2 of an fp32 parameter gradient summed from the kernels' partials (AdaLN's d scale sums the
+}                         # bf16-rounded LN output: its rounding flips put the kernel at 2e-5)
+
+
+def scene_meta(text_length, num_chunks, num_frames, H, W):
+    """SequenceMetadata of ``num_chunks`` scenes of ``text_length`` text tokens over ``num_frames`` H x W latent frames"""
+    from ttt_amd.models.cogvideo.utils import SequenceMetadata
+    meta = SequenceMetadata(text_length=text_length, seq_text_length=num_chunks * text_length, num_frames=num_frames,
+                            num_chunks=num_chunks, tokens_per_frame=H * W, latent_height=H, latent_width=W, t_emb=torch.zeros(1))
+    if meta.is_multiscene:
+        meta.init_multiscene_offsets()
+    return meta
+
+
+def glue_maps(meta, reverse=False):
+    """(L, src, pos, rope) of the fused pre / post kernels for ``meta``, from the module's own ``TTTBase._token_maps`` and RoPE
+    table (head_dim 64, the video fills every row of the table: its last row is used)"""
+    import types
+    from ttt_amd.models.ssm.ttt_layer import TTTBase
+    from ttt_amd.models.ssm.utils import precompute_freqs_cis_3d
+    L = meta.seq_text_length + meta.num_frames * meta.tokens_per_frame
+    src, pos, _ = TTTBase._token_maps(types.SimpleNamespace(_perm_cache={}), meta, L, "cpu", reverse)
+    rope = precompute_freqs_cis_3d(64, meta.latent_height, meta.latent_width, meta.num_frames, as_real=True)
+    return L, src, pos, rope
+
+
 def tile_states(d, B):
     t = lambda w: torch.tile(w.unsqueeze(0), dims=(B, 1, 1, 1)).contiguous()
     return {k: t(d[k]) for k in ("W1", "b1", "W2", "b2") if k in d}

@@ -73,6 +73,23 @@ GLUE_TOL = {
     "psum": 1e-4,         # rel-L2 of an fp32 parameter gradient summed from the kernels' partials (AdaLN's d scale sums the
 }                         # bf16-rounded LN output: its rounding flips put the kernel at 2e-5)
 
+# Tolerances of the segment-attention kernels against oracle/attn_oracle.py (tests/test_attention_oracle_gpu.py), fixed by the
+# sensitivity table of tests/test_attention_oracle_cpu.py in the same way: >= 10x the oracle's own fp32-vs-fp64 distance, >= 10x
+# below every mutation the table marks as one the metric must catch.
+ATTN_TOL = {
+    "ulp_frac": 2e-3,     # fraction of bf16 outputs (O, dQ, dK, dV, q, k, dq_raw, dk_raw) more than 1 ulp from the statement
+    "ulp_max": 64.0,      # largest distance in ulps (floor: 1/8 of the reference's RMS)
+    "row": 3e-2,          # worst rel-L2 of one (batch, head, token) row against the bf16-rounded statement
+    "lse": 5e-5,          # largest |LSE - LSE_ref| (natural-log units)
+    "delta": 1e-6,        # largest |Delta - Delta_ref| / sum |O dO| of the row
+    "psum": 2e-5,         # rel-L2 of a LayerNorm parameter gradient summed (fp64) from the pre kernel's [P, 4, 64] partials
+    "cancel": 1e-3,       # rel-L2 of the dQ / dK error against the size of the terms they sum (attn_cases.cancel_err): the regimes
+}                         # where those terms cancel (a saturated softmax, equal keys, |LSE| ~ 1e3, S = 1)
+# Scores offset by |LSE| ~ 1e3 (attn_cases.large_lse_case): fp32 keeps ~1e-4 raw-score units of such a score, and the dK / dV
+# kernel starts its accumulator from -LSE / scale; dQ = sum dS K cancels the shared key direction.  The table's fp32 row for that
+# regime sets these (the other metrics as ATTN_TOL).
+ATTN_TOL_LARGE = dict(ATTN_TOL, ulp_frac=5e-3, row=5e-2, lse=5e-4)
+
 
 def scene_meta(text_length, num_chunks, num_frames, H, W):
     """SequenceMetadata of ``num_chunks`` scenes of ``text_length`` text tokens over ``num_frames`` H x W latent frames"""

@@ -14,8 +14,11 @@
 //     (Peeling the last tile into a second instantiation of the loop body does the same but made the register allocator
 //     spill in the 128-register dQ kernel; this form keeps revision 1's loop shape.)
 // Everything else - the arithmetic, its order, the rounding points - is revision 1's (in the dQ kernel a masked score is set
-// to -1e30 before the exponential instead of zeroing the probability after it: exp2(-1e30 ...) == 0 exactly), so the two
-// revisions agree bit for bit (tests/test_attention_gpu.py::test_attention_v2_equals_v1).
+// to -1e30 before the exponential instead of zeroing the probability after it: exp2(-1e30 ...) == 0 exactly).
+// Shipped on the device: the revision-1 forward (attn_fwd.hip), and from this file dq_wide() and dkdv_staged<12, true, 2>()
+// (attn_v2.hip); forward() here runs only on the emulator.  tests/test_attention_oracle_gpu.py pins the device kernels to the
+// rounding-aware fp64 statements of oracle/attn_oracle.py; tests/test_attention_oracle_cpu.py holds forward(), dq_wide() and
+// dkdv_staged() on the emulator to the same tolerances.
 //
 // Backend contract: lane(), wave(), thread(), barrier(), exp2(), log(); tile_t = element pointer into LDS with lds_base(),
 // ld<T>(ptr), st(ptr, v), tr(ptr) = ds_read_b64_tr_b16; mma3216(a, b, c) = v_mfma_f32_32x32x16_bf16; xor_read(v, mask) = the value

@@ -155,10 +155,12 @@ int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* wor
 /* An extension BESIDE the 15-tensor forward (round 5), not instead of it: the TTT-MLP forward over steps [step0, step0 + nsteps)
  * of the sequence that `d` and `a` describe (d->NC = the whole sequence; the tensors of `a` are the whole sequence's), started
  * from the state in a->W1_init .. b2_init and leaving the state after its last step in W1_final .. b2_final ([B,NH,...] fp32 like
- * the initial state; may alias it; all four NULL: not stored).  Parts start and end at checkpoint-group boundaries (step0 % G
- * == 0); their outputs and checkpoints land where the one-call forward puts them, with the same bits (the state is handed on
- * in fp32, exactly as the kernel holds it).  Lets a caller run the projections of the next part of the sequence on the CUs the
- * sequential scan leaves idle (ttt_amd/models/ssm/pipeline.py).  MFMA scan at mini-batches of 64 only. */
+ * the initial state; may alias it; all four NULL: not stored).  At mini-batches of 64, parts start and end at checkpoint-group
+ * boundaries (step0 % G == 0); at mini-batches of 16 (the sampling geometry: one checkpoint group for the whole sequence) a part
+ * is any [step0, step0 + nsteps) inside [0, NC) and the workspace arguments are not used (ttt_hip_mlp_forward_workspace is 0
+ * there).  Outputs and checkpoints land where the one-call forward puts them, with the same bits (the state is handed on in
+ * fp32, exactly as the kernel holds it).  Lets a caller run the projections of the next part of the sequence on the CUs the
+ * sequential scan leaves idle (ttt_amd/models/ssm/pipeline.py).  MFMA scan only (mini-batches of 64 or 16). */
 int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                               float* W2_final, float* b2_final, void* workspace, size_t workspace_bytes, void* stream);
 int ttt_hip_linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* workspace, size_t workspace_bytes, void* stream);

@@ -1,13 +1,15 @@
 """Sampling-path measurement ("Sampling (cfg 5): latent frames/s"; 8f #3) on one MI355X.
 
-    python tools/sample_bench.py [--video-length 3sec] [--steps 3] [--layers 42] [--sequential]
+    python tools/sample_bench.py [--video-length 3sec] [--steps 3] [--layers 42] [--sequential] [--pipeline-parts N] [--ab ROUNDS]
 
 CogVideoX-5B + TTT-MLP in bf16 with the evaluation settings of the reference (configs/eval/ttt-mlp/*.toml:
 mini_batch_size = 16, no scan checkpoints), random-init weights and synthetic text embeddings, driven by the mirrored
 DPM-Solver++(2M) sampler (ttt_amd/models/cogvideo/sampling.py).  A denoising step is one network evaluation on the
 classifier-free-guidance pair: one batch of two here, two batch-1 calls with --sequential (the reference's order,
 cogvideo/utils.py:478-492).  Prints one JSON line: seconds per denoising step and latent frames/s, with the 50-step
-projection.
+projection.  --pipeline-parts N: the TTT layers' forward as a pipeline over exactly N parts (0 = one piece; default: the
+library's plan).  --ab ROUNDS: one piece and the default plan alternated inside this process, ROUNDS times each, every arm's
+per-step times listed (the one-piece arm's spread is the yardstick for the difference).
 """
 import argparse
 import json
@@ -34,6 +36,10 @@ def main():
                     help="launched with torch.distributed.run on N GPUs: one video sampled by N ranks (token shards for the "
                          "token-wise work, head shards for attention / the TTT scan; ttt_amd/infra/sequence_parallel.py)")
     ap.add_argument("--no-warmup", action="store_true", help="skip the untimed step (long videos: the timed steps then include one-time costs)")
+    ap.add_argument("--pipeline-parts", type=int, default=None,
+                    help="TTT layer forward as a pipeline over exactly N parts of the sequence; 0 = one piece (default: the library's plan)")
+    ap.add_argument("--ab", type=int, default=0, metavar="ROUNDS",
+                    help="alternate one piece / the default plan inside this process, ROUNDS timed runs of --steps steps each")
     a = ap.parse_args()
 
     import test_time_training as ext
@@ -77,6 +83,15 @@ def main():
         layer.seq_modeling_block.rotary.init_freqs()
         layer.seq_modeling_block.ssm.init_freqs()
 
+    from ttt_amd.models.ssm.ttt_layer import TTTBase
+    ttts = [m for m in net.modules() if isinstance(m, TTTBase)]
+    default_plan = [(m.pipeline_parts, m.pipeline_parts_auto) for m in ttts]
+
+    def set_parts(n):                                       # None: the library default
+        for m, (n0, auto0) in zip(ttts, default_plan):
+            m.pipeline_parts, m.pipeline_parts_auto = (n0, auto0) if n is None else (n, False)
+
+    set_parts(a.pipeline_parts)
     L = frames * 1350 + scenes * text_len
     NC = L // 16
     impl = ext.resolved_impl(2, cfg.num_heads, NC, 16, 64, NC, torch.bfloat16, mlp=True, backward=False)
@@ -96,6 +111,28 @@ def main():
         torch.cuda.synchronize()
         return out
 
+    if a.ab:
+        arms = {"one_piece": 0, "default": None}
+        times = {k: [] for k in arms}
+        for k, n in arms.items():                            # warm-up of both arms: GEMM selection per shape, allocator
+            set_parts(n)
+            run(1)
+        for _ in range(a.ab):
+            for k, n in arms.items():
+                set_parts(n)
+                t0 = time.perf_counter()
+                out = run(a.steps)
+                times[k].append(round((time.perf_counter() - t0) / a.steps, 4))
+                assert torch.isfinite(out).all()
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        if rank == 0:
+            print(json.dumps({"metric": "sampling_denoising_step_seconds_ab", "unit": "s/step (cond+uncond)", "median": med, "runs": times,
+                              "one_piece_spread": round(max(times["one_piece"]) - min(times["one_piece"]), 4),
+                              "default_minus_one_piece": round(med["default"] - med["one_piece"], 4),
+                              "config": {"video_length": a.video_length, "layers": cfg.num_layers, "steps_per_run": a.steps, "tokens": L,
+                                         "mini_batches": NC, "scan_impl": impl},
+                              "peak_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}))
+        return
     if not a.no_warmup:
         run(1)                                               # warm-up: GEMM selection, allocator
     t0 = time.perf_counter()
@@ -109,7 +146,8 @@ def main():
                       "config": {"workload": f"CogVideoX-5B+TTT-MLP sampling, {a.video_length}, CS=16, CFG pair "
                                              + ("sequential" if a.sequential else "batched")
                                              + (f", sequence-parallel over {int(os.environ.get('WORLD_SIZE', '1'))} ranks" if a.sequence_parallel else ""),
-                                 "layers": cfg.num_layers, "timed_steps": a.steps, "warmup": not a.no_warmup, "tokens": L, "mini_batches": NC, "scan_impl": impl},
+                                 "layers": cfg.num_layers, "timed_steps": a.steps, "warmup": not a.no_warmup, "tokens": L, "mini_batches": NC, "scan_impl": impl,
+                                 "pipeline_parts": "default" if a.pipeline_parts is None else a.pipeline_parts},
                       "dtype": "bf16", "data": "synthetic", "peak_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}))
 
 

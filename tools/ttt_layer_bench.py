@@ -4,6 +4,13 @@ geometry as one piece and as a pipeline over parts of the sequence (ttt_amd/mode
 process, medians, forward alone and forward + backward; outputs / gradients compared.
 
     python tools/ttt_layer_bench.py [--parts 0,2,3,4] [--video-length 9sec] [--rounds 5]
+
+The sampling geometry (mini-batches of 16, one checkpoint group, the guidance pair as a batch of two, forward only):
+
+    python tools/ttt_layer_bench.py --mini-batch 16 --batch 2 --no-grad --video-length 63sec --parts 0,default,4,8,16
+
+("default" = the library's plan; at mini-batches of 16 a number means exactly that many parts).  --scan-only times the scans
+alone: the one-call forward against the same scan as the chunk launches of each plan, back to back on one stream.
 """
 import argparse
 import json
@@ -26,11 +33,61 @@ def timeit(fn, iters=3):
     return ms[len(ms) // 2]
 
 
+def scan_only(a, ext, layer, meta, x, L, parts, set_parts, res):
+    """the scan kernels alone at this geometry (random inputs): ttt_forward against the chunk launches of each plan"""
+    dev = x.device
+    B, NH, CS, Fh = x.shape[0], layer.ttt.num_heads, a.mini_batch, 64
+    NC = L // CS
+    G = layer.ttt._group_size(NC)
+    K = -(-NC // G)
+    g = torch.Generator(device=dev).manual_seed(3)
+    mk = lambda *s, scale=1.0: torch.randn(*s, device=dev, generator=g) * scale
+    l2 = lambda t: torch.nn.functional.normalize(t, dim=-1)
+    XQ, XK, XV = l2(mk(B, NH, NC, CS, Fh)).bfloat16(), l2(mk(B, NH, NC, CS, Fh)).bfloat16(), mk(B, NH, NC, CS, Fh, scale=0.5).bfloat16()
+    eta = (torch.rand(B, NH, NC, CS, 1, device=dev, generator=g) * 0.02 + 0.005).bfloat16()
+    lw, lb = (1 + 0.1 * mk(1, NH, 1, Fh)).float(), (0.1 * mk(1, NH, 1, Fh)).float()
+    st = [mk(B, NH, Fh, 4 * Fh, scale=0.02), mk(B, NH, 1, 4 * Fh, scale=0.02), mk(B, NH, 4 * Fh, Fh, scale=0.02), mk(B, NH, 1, Fh, scale=0.02)]
+    e32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+    cks = (e32(B, NH, K, Fh, 4 * Fh), e32(B, NH, K, 1, 4 * Fh), e32(B, NH, K, 4 * Fh, Fh), e32(B, NH, K, 1, Fh))
+    out0, out1 = torch.empty_like(XQ), torch.empty_like(XQ)
+
+    def one_call():
+        ext.ttt_forward(XQ, XK, XV, eta, lw, lb, *st, *cks, out0, G)
+
+    def in_parts(plan):
+        carry = [t.clone() for t in st]
+        for s0, ns, _ in plan:
+            ext.ttt_forward_chunk(XQ, XK, XV, eta, lw, lb, *carry, *cks, out1, G, s0, ns)
+
+    plans = {}
+    for n in parts:
+        set_parts(n)
+        with torch.no_grad():
+            plans[n] = layer.ttt._pipeline_plan(x, meta, L, False, False)
+    t = {n: [] for n in parts}
+    for _ in range(a.rounds):
+        for n in parts:
+            t[n].append(timeit(one_call if plans[n] is None else (lambda: in_parts(plans[n]))))
+    for n in parts:
+        ent = {"scan_ms_median": sorted(t[n])[len(t[n]) // 2], "scan_ms_runs": [round(v, 3) for v in t[n]],
+               "launches": 1 if plans[n] is None else len(plans[n])}
+        if plans[n] is not None:
+            one_call(); in_parts(plans[n]); torch.cuda.synchronize()
+            ent["bits_of_one_call"] = bool(torch.equal(out0, out1))
+        res["by_parts"][str(n)] = ent
+    res["scan"] = {"B": B, "NH": NH, "NC": NC, "G": G}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="0,2,3,4")
     ap.add_argument("--video-length", default="9sec")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--mini-batch", type=int, default=64, choices=[64, 16], help="16: the evaluation settings (no scan checkpoints)")
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--no-grad", action="store_true", help="forward only (required at mini-batches of 16: no MFMA backward there)")
+    ap.add_argument("--scan-only", action="store_true", help="time the scan kernels alone: one call against the parts of each plan")
     ap.add_argument("--tuning-file", default=None, help="GEMM solution selections to load instead of the committed ttt_amd/infra/gemm_tuning_gfx950.csv")
     ap.add_argument("--debug-option", action="append", default=[], metavar="NAME=VALUE", help="library debug option(s) for the whole run (e.g. scan_pair=0)")
     a = ap.parse_args()
@@ -45,7 +102,10 @@ def main():
         ext.debug_option(kv.split("=")[0], int(kv.split("=")[1]))
     dev = torch.device("cuda:0")
     tuned = enable_tuned_gemms(a.tuning_file)
-    cfg = ModelConfig.get_preset("5B", a.video_length, ssm_layer="ttt_mlp", adapter_method="qkvo")
+    if a.mini_batch == 16 and not a.no_grad:
+        ap.error("--mini-batch 16 needs --no-grad")
+    over = {"mini_batch_size": 16, "scan_checkpoint_group_size": 10 ** 6} if a.mini_batch == 16 else {}
+    cfg = ModelConfig.get_preset("5B", a.video_length, ssm_layer="ttt_mlp", adapter_method="qkvo", **over)
     frames, tl = cfg.compressed_num_frames, TEXT_LEN[a.video_length]
     scenes = max((frames - 1) // 12, 1)
     n_vid = frames * TOKENS_PER_FRAME
@@ -59,21 +119,53 @@ def main():
     if meta.is_multiscene:
         meta.init_multiscene_offsets()
     g = torch.Generator(device=dev).manual_seed(1)
-    x = torch.randn(1, L, cfg.model_dim, device=dev, generator=g).bfloat16().requires_grad_(True)
-    dy = torch.randn(1, L, cfg.model_dim, device=dev, generator=g).bfloat16() * 0.1
+    x = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16().requires_grad_(not a.no_grad)
+    dy = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16() * 0.1
     params = [p for p in layer.parameters() if p.requires_grad]
-    parts = [int(v) for v in a.parts.split(",")]
-    res = {"L": L, "tuned_gemms": bool(tuned), "by_parts": {}}
+    parts = [v if v == "default" else int(v) for v in a.parts.split(",")]
+    res = {"L": L, "batch": a.batch, "mini_batch": a.mini_batch, "tuned_gemms": bool(tuned), "by_parts": {}}
+    default_plan = (layer.ttt.pipeline_parts, layer.ttt.pipeline_parts_auto)
+
+    def set_parts(n):
+        if n == "default":
+            layer.ttt.pipeline_parts, layer.ttt.pipeline_parts_auto = default_plan
+        else:
+            layer.ttt.pipeline_parts = n
+            layer.ttt.pipeline_parts_auto = default_plan[1] and a.mini_batch == 64      # (CS = 64: "at least n", as always)
 
     def fwd(n, reverse):
-        layer.ttt.pipeline_parts = n
+        set_parts(n)
         with torch.no_grad():
             return layer(x, meta, reverse)
 
     def fwd_bwd(n, reverse):
-        layer.ttt.pipeline_parts = n
+        set_parts(n)
         y = layer(x, meta, reverse)
         return y, torch.autograd.grad(y, [x] + params, dy)
+
+    if a.scan_only:
+        return scan_only(a, ext, layer, meta, x, L, parts, set_parts, res)
+    if a.no_grad:
+        t = {n: {"fwd": [], "fwd_rev": []} for n in parts}
+        for _ in range(a.rounds):
+            for n in parts:
+                t[n]["fwd"].append(timeit(lambda: fwd(n, False)))
+                t[n]["fwd_rev"].append(timeit(lambda: fwd(n, True)))
+        rl2 = lambda p, q: float((p.double() - q.double()).norm() / q.double().norm().clamp_min(1e-30))
+        ref = {rev: fwd(parts[0], rev) for rev in (False, True)}
+        for n in parts:
+            ent = {"median_ms": {k: sorted(v)[len(v) // 2] for k, v in t[n].items()}, "runs_ms": {k: [round(u, 3) for u in v] for k, v in t[n].items()}}
+            set_parts(n)
+            with torch.no_grad():
+                plan = layer.ttt._pipeline_plan(x, meta, L, False, False)
+            ent["part_steps"] = None if plan is None else [p[1] for p in plan]
+            if n != parts[0]:
+                for rev in (False, True):
+                    y = fwd(n, rev)
+                    ent["reverse" if rev else "forward"] = {"out_equal": bool(torch.equal(y, ref[rev])), "out_rel_l2": rl2(y, ref[rev])}
+            res["by_parts"][str(n)] = ent
+        print(json.dumps(res))
+        return
 
     t = {n: {"fwd": [], "fwd_rev": [], "fwd_bwd": []} for n in parts}
     for _ in range(a.rounds):

@@ -166,9 +166,12 @@ int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int 
     NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
     NEED(W1_init); NEED(b1_init); NEED(W2_init); NEED(b2_init);
     NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints); NEED(XQW);
-    if (resolve(d, true, false) != TTT_IMPL_MFMA || d->CS != 64)
-        return fail("ttt_hip: mlp_forward_chunk: only the MFMA scan at mini-batches of 64 continues from a state");
-    if (step0 < 0 || nsteps <= 0 || step0 + nsteps > d->NC || step0 % d->G != 0 || ((step0 + nsteps) % d->G != 0 && step0 + nsteps != d->NC))
+    if (resolve(d, true, false) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
+        return fail("ttt_hip: mlp_forward_chunk: only the MFMA scan (mini-batches of 64 or 16) continues from a state");
+    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
+        return fail("ttt_hip: mlp_forward_chunk: the part [step0, step0 + nsteps) must lie inside [0, NC)");
+    // CS = 64 hands over at checkpoint-group boundaries; the CS = 16 scan (one group in sampling) continues from any step
+    if (d->CS == 64 && (step0 % d->G != 0 || ((step0 + nsteps) % d->G != 0 && step0 + nsteps != d->NC)))
         return fail("ttt_hip: mlp_forward_chunk: a part of the sequence starts and ends at checkpoint-group boundaries (or at the end)");
     if ((W1_final || b1_final || W2_final || b2_final) && !(W1_final && b1_final && W2_final && b2_final))
         return fail("ttt_hip: mlp_forward_chunk: give all four final-state buffers or none");

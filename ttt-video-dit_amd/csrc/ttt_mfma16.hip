@@ -154,11 +154,12 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void linear_scan16_kernel(wv::Lin16
     lin16::forward(bk, p, bh);
 }
 
-// TTT-MLP forward scan at mini-batches of 16: the backend-templated workgroup body of ttt_mlp16_body.h
-__global__ __launch_bounds__(NT16) void mlp_scan16_body_kernel(wv::Mlp16Params p) {
+// TTT-MLP forward scan at mini-batches of 16: the backend-templated workgroup body of ttt_mlp16_body.h, over the whole sequence
+// or a part of it (one kernel for both: the one-call scan is the part [0, NC) without a final-state store)
+__global__ __launch_bounds__(NT16) void mlp_scan16_body_kernel(wv::Mlp16ChunkParams c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     DeviceWave bk{smem};
-    mlp16::forward(bk, p, blockIdx.x);
+    mlp16::forward_part(bk, c, blockIdx.x);
 }
 
 // backward: one wave per workgroup (48 .. 96 scans on 256 CUs: a CU of its own per scan; up to 512 registers per lane)
@@ -192,11 +193,17 @@ void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*
     done.run([&] {
         (void)hipFuncSetAttribute((const void*)v16::mlp_scan16_body_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::GROUP_LDS);
     });
-    wv::Mlp16Params q = {};
+    // a part of the sequence (mlp_forward_chunk): p.NC steps from step p.ck0 of p.NCs, the pointers those of the whole sequence
+    // (at CS = 16 a part may start at any step, so ck0 carries the first STEP, not a checkpoint index).  p.NCs == 0: one call.
+    const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
+    wv::Mlp16ChunkParams c = {};
+    wv::Mlp16Params& q = c.p;
     q.XQ = p.XQ; q.XK = p.XK; q.XV = p.XV; q.eta = p.eta; q.ln_w = p.ln_w; q.ln_b = p.ln_b;
     q.W1 = p.W1; q.b1 = p.b1; q.W2 = p.W2; q.b2 = p.b2; q.W1c = p.W1c; q.b1c = p.b1c; q.W2c = p.W2c; q.b2c = p.b2c;
     q.out = p.out; q.NH = p.NH; q.NC = p.NC; q.G = p.G; q.K = p.K; q.eps = p.eps;
-    hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, q);
+    c.step0 = step0; c.NCs = NCs;
+    c.W1f = p.W1f; c.b1f = p.b1f; c.W2f = p.W2f; c.b2f = p.b2f;
+    hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, c);
 }
 
 }  // namespace mfma

@@ -19,6 +19,7 @@ struct ScanParams {
     // a launch over a PART of the sequence (round 5, ttt_hip_mlp_forward_chunk): NC steps starting at a checkpoint-group boundary.
     // The tile pointers are pre-offset to the first step; consecutive heads are NCs tiles apart (0: NC), checkpoint index ck0 + i / G,
     // the state after the last step goes to W1f .. b2f ([B,NH,...] like the initial state, may alias it; null: not stored).
+    // CS = 16 (launch_scan_forward_cs16): a part starts at ANY step; the pointers stay those of the whole sequence and ck0 is the first step.
     int NCs, ck0;
     float *W1f, *b1f, *W2f, *b2f;
     unsigned long long* dbg;               // optional per-phase cycle totals of workgroup 0

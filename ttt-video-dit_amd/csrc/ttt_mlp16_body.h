@@ -66,11 +66,40 @@ TTT_WV_FN void row_stats(BK& bk, f32x4 z, float eps, float& mu, float& rstd) {
     rstd = bk.rsq(bk.sum16(v) * (1.0f / 64.0f) + eps);
 }
 
+// this wave's share of the fp32 state in the layout of the initial state: a checkpoint, or the state a part hands on.  W2 is
+// stored from its [f][n] accumulators (W2Tt); a restart fills both orientations from that one array.
+TTT_WV_FN void store_state(float* W1g, float* b1g, float* W2g, float* b2g, const f32x4 (&W1t)[4][2], const f32x4 (&W2Tt)[4][2],
+                           const float (&b1v)[2], const float (&b2v)[4], int wv, int g, int i) {
+    const int n0 = 32 * wv;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) W1g[(size_t)(16 * fb + 4 * g + r) * 256 + n0 + 16 * nb + i] = W1t[fb][nb][r];
+            *reinterpret_cast<f32x4*>(W2g + (size_t)(n0 + 16 * nb + i) * 64 + 16 * fb + 4 * g) = W2Tt[fb][nb];
+        }
+    if (g == 0) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) b1g[n0 + 16 * nb + i] = b1v[nb];
+        if (wv == 0) {
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) b2g[16 * fb + i] = b2v[fb];
+        }
+    }
+}
+
+// Steps [c.step0, c.step0 + c.p.NC) of a scan of c.NCs steps (Mlp16ChunkParams, ttt_wave_types.h).  `it` counts the steps of
+// the PART: the LDS buffers rotate on it and the two-tile prefetch clamps to the part's last tile, so a part never reads an
+// input outside itself; only the checkpoint rule looks at the step's place in the whole sequence.  Everything a step takes
+// from the one before it is rebuilt from the fp32 state (W1F / W2F / the b2 copy in LDS), so a part that starts from the state
+// another part stored continues that scan bit for bit.
 template <class BK>
-TTT_WV_FN void forward(BK& bk, const Mlp16Params& p, int bh) {
+TTT_WV_FN void forward_part(BK& bk, const Mlp16ChunkParams& c, int bh) {
+    const Mlp16Params& p = c.p;
     const int tid0 = bk.thread(), wv = bk.wave(), l0 = bk.lane();
     const int n0 = 32 * wv, img = L_IMG + wv * IMG_BYTES;
-    const int NC = p.NC, G = p.G, head = bh % p.NH;
+    const int NC = p.NC, G = p.G, head = bh % p.NH, step0 = c.step0;
 
     f32x4 W1t[4][2], W2t[2][4], W2Tt[4][2];      // (rows = f, lane = n) ; (rows = n, lane = f) ; (rows = f, lane = n)
     float b1v[2], b2v[4];
@@ -109,7 +138,7 @@ TTT_WV_FN void forward(BK& bk, const Mlp16Params& p, int bh) {
     for (int fb = 0; fb < 4; ++fb) W2F[fb] = stack(W2t[0][fb], W2t[1][fb]);
 
     // input staging: thread groups of 128 move one 16-byte chunk of K / V / Q (waves 6, 7 mirror Q's loads and do not store)
-    const size_t tile0 = (size_t)bh * NC;
+    const size_t tile0 = (size_t)bh * c.NCs + step0;
     const int which = wv >> 1;
     const __bf16* src = which == 0 ? p.XK : which == 1 ? p.XV : p.XQ;
     const int dstb = which == 0 ? L_K : which == 1 ? L_V : L_Q;
@@ -144,26 +173,9 @@ TTT_WV_FN void forward(BK& bk, const Mlp16Params& p, int bh) {
         f32x4 D1[2];
         bf16x4 X2p[2];
         if (live) {
-            if (it % G == 0) {
-                const size_t ck = (size_t)bh * p.K + it / G;
-                float* W1g = p.W1c + ck * 64 * 256;
-                float* W2g = p.W2c + ck * 256 * 64;
-#pragma unroll
-                for (int fb = 0; fb < 4; ++fb)
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) W1g[(size_t)(16 * fb + 4 * g + r) * 256 + n0 + 16 * nb + i] = W1t[fb][nb][r];
-                        *reinterpret_cast<f32x4*>(W2g + (size_t)(n0 + 16 * nb + i) * 64 + 16 * fb + 4 * g) = W2Tt[fb][nb];
-                    }
-                if (g == 0) {
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) p.b1c[ck * 256 + n0 + 16 * nb + i] = b1v[nb];
-                    if (wv == 0) {
-#pragma unroll
-                        for (int fb = 0; fb < 4; ++fb) p.b2c[ck * 64 + 16 * fb + i] = b2v[fb];
-                    }
-                }
+            if ((step0 + it) % G == 0) {
+                const size_t ck = (size_t)bh * p.K + (step0 + it) / G;
+                store_state(p.W1c + ck * 64 * 256, p.b1c + ck * 256, p.W2c + ck * 256 * 64, p.b2c + ck * 64, W1t, W2Tt, b1v, b2v, wv, g, i);
             }
             // A1: Z1 = K W1 + b1 ; X2, D1 (rows = t, lane = n) ; X2 image [n][t]
             const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
@@ -297,6 +309,21 @@ TTT_WV_FN void forward(BK& bk, const Mlp16Params& p, int bh) {
             for (int fb = 0; fb < 4; ++fb) bk.template lds_store<float>(L_B2 + (16 * fb + i) * 4, b2v[fb]);
         }
     }
+    if (c.W1f) {      // hand the state on (may overwrite the initial state: every wave read its slice before the first barrier)
+        const int l = bk.opaque(l0);
+        store_state(c.W1f + (size_t)bh * 64 * 256, c.b1f + (size_t)bh * 256, c.W2f + (size_t)bh * 256 * 64, c.b2f + (size_t)bh * 64,
+                    W1t, W2Tt, b1v, b2v, wv, l >> 4, l & 15);
+    }
+}
+
+// the whole sequence in one call
+template <class BK>
+TTT_WV_FN void forward(BK& bk, const Mlp16Params& p, int bh) {
+    Mlp16ChunkParams c = {};
+    c.p = p;
+    c.step0 = 0;
+    c.NCs = p.NC;
+    forward_part(bk, c, bh);
 }
 
 }  // namespace mlp16

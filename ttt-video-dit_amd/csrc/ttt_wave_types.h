@@ -43,5 +43,15 @@ struct Mlp16Params {
     float eps;
 };
 
+// the same scan over a PART of the sequence: steps [step0, step0 + p.NC) of a sequence of NCs steps.  The pointers of `p` are
+// those of the whole sequence (consecutive heads NCs tiles apart, K = ceil(NCs / G) checkpoints per head); p.W1 .. p.b2 hold the
+// state entering step0; the state after the last step of the part goes to W1f .. b2f (layout of the initial state, may alias
+// it; all null: not stored).  step0 = 0, NCs = p.NC, no final state: the one-call scan.
+struct Mlp16ChunkParams {
+    Mlp16Params p;
+    int step0, NCs;
+    float *W1f, *b1f, *W2f, *b2f;
+};
+
 }  // namespace wv
 }  // namespace ttt

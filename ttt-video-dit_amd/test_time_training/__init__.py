@@ -332,7 +332,8 @@ def ttt_forward_chunk(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_s
     """The TTT-MLP forward over steps [step0, step0 + nsteps) of the sequence the (whole-sequence) tensors describe - an extension
     beside ``ttt_forward``'s 15-tensor call (``ttt_hip_mlp_forward_chunk``): started from the fp32 state in ``*_state``
     ([B,NH,F,H], [B,NH,1,H], [B,NH,H,F], [B,NH,1,F]), which it REPLACES by the state after its last step, so that consecutive
-    calls walk the sequence with the bits of the one-call forward.  Parts start at checkpoint-group boundaries."""
+    calls walk the sequence with the bits of the one-call forward.  MFMA scan only.  At mini-batches of 64 parts start and end at
+    checkpoint-group boundaries (or at the end); at mini-batches of 16 a part is any [step0, step0 + nsteps) inside [0, NC)."""
     _check5(XQ)
     B, NH, NC, CS, F = XQ.shape
     G = int(checkpoint_group_size)

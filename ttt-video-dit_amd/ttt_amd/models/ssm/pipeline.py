@@ -8,6 +8,8 @@ previous part left and hands its own on in fp32 - the bits of the one-call scan)
 pre-processing of part c + 1 and the post-norm + output projection of part c - 1.  The pre- / post-processing kernels take a range
 of scan positions (``ttt_hip_pre_forward_range`` / ``ttt_hip_post_forward_range``); the GEMMs work on the token runs a part covers
 (a part is a few contiguous runs of the [texts | video] sequence: the scan order interleaves scenes and may be time-reversed).
+At mini-batches of 16 (sampling, ``no_grad``) there is one checkpoint group for the whole sequence; the CS = 16 scan continues from any
+step, and the parts are multiples of a step quantum instead (CS16_QUANTUM below).
 
 This is FORWARD work only and changes no autograd node: the pre-pass runs under ``no_grad`` and fills the very tensors the layer's
 autograd Functions would produce (raw projections, scan output + state checkpoints, post-norm output, layer output); the Functions
@@ -97,6 +99,20 @@ class InjectedLinear(torch.autograd.Function):
 # towards the end cut that tail; a two-resource model of the timeline fitted to the trace puts the optimum for four parts near these
 # shares (6.26 against 6.50 ms).  TTT_PIPELINE_WEIGHTS="w0,w1,..." overrides (A/B knob; "equal" = the round-5 plan).
 TAPER = {4: (0.31, 0.33, 0.24, 0.12), 5: (0.31, 0.31, 0.22, 0.12, 0.04), 6: (0.26, 0.27, 0.21, 0.14, 0.08, 0.04)}
+
+
+# Mini-batches of 16 under no_grad (sampling): the reference samples with one checkpoint group for the whole sequence, so there is no
+# group boundary to cut at; the CS = 16 scan continues from ANY step (ttt_hip_mlp_forward_chunk) and the plan cuts at multiples of a
+# step quantum: 256 steps = 4 096 tokens, a row block the GEMMs run at full rate.  Here the SCAN is the longer leg (55.7 ms against
+# ~47 ms of GEMMs + glue per layer forward at 63 s, batch 2), so what stays exposed is the first part's projections and the last part's
+# post-norm + output projection: up to CS16_PARTS parts of at least three quanta, tapered like the long CS = 64 plans
+# (part_group_counts).  Measured on one MI355X, interleaved in one process (profiles/r7_cs16_parts_*): layer forward at 63 s
+# 102.4 ms as one piece, 76.9 (8 parts), 78.2 (4), 78.1 (16); at 9 s 15.6 / 11.5 (4) / 12.0 (6).  The scan alone costs 55.66 ms in one
+# call and 55.79 ms as 8 launches (17 us per extra launch: launch latency + the 260 KiB state re-read and stored per head).  Scans
+# shorter than CS16_MIN_STEPS (eight quanta, like the eight checkpoint groups at CS = 64; the 3 s video has 1 158 steps) stay one piece.
+CS16_QUANTUM = 256
+CS16_MIN_STEPS = 8 * CS16_QUANTUM
+CS16_PARTS = 8
 
 
 def part_group_counts(K: int, n_parts: int):

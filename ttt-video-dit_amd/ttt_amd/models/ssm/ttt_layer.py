@@ -137,7 +137,9 @@ class TTTBase(nn.Module):
         # Round 6, with the pair scan (the compute stream became the pipeline's co-bottleneck): 5 parts that TAPER towards the end
         # (pipeline.TAPER: 16 / 16 / 11 / 6 / 2 of 51 checkpoint groups at 9 s) - in-step 8 554 - 8 574 against 8 484 - 8 501 video-tok/s for
         # 4 equal parts on one box (+0.8 %), 4 tapered parts the same as 4 equal (profiles/r6ab2_*).  Fewer parts where the scan has
-        # fewer than two checkpoint groups per part; on the MFMA scan at CS = 64 only.
+        # fewer than two checkpoint groups per part; on the MFMA scan only.
+        # At CS = 16 (sampling: one checkpoint group) the forward is pipelined under no_grad, cut at multiples of a step quantum
+        # (pipeline.CS16_QUANTUM / CS16_PARTS / CS16_MIN_STEPS); with grad enabled CS = 16 stays one piece.
         self.pipeline_parts = int(os.environ.get("TTT_PIPELINE_PARTS", "5"))
         # ... and more of them for long scans (up to 8, one per ~40 checkpoint groups): what stays exposed is the first part's projections
         # and the last part's output projection, which grow with the sequence - at 63 s (343 groups) 8 parts measured 7 122 against 7 001
@@ -390,33 +392,47 @@ class TTTBase(nn.Module):
 
     def _pipeline_plan(self, x, meta, L, reverse, heads_only):
         """the parts of a pipelined forward, or None when this call runs as one piece: not TTT-MLP on the MFMA scan at mini-batches of
-        64, fewer than two checkpoint groups per part, a head shard, a re-materialisation that gets its scan result handed back"""
+        64 or (forward only, under ``no_grad``) of 16, a scan too short to cut, a head shard, a re-materialisation that gets its scan
+        result handed back"""
         from ttt_amd.infra import remat_cache
+        from ttt_amd.models.ssm import pipeline
         n = self.pipeline_parts
         CS = self.mini_batch_size
-        if n < 2 or heads_only or not isinstance(self, TTTMLP) or CS != 64 or remat_cache.replaying("scan"):
+        if n < 2 or heads_only or not isinstance(self, TTTMLP) or CS not in (64, 16) or remat_cache.replaying("scan"):
+            return None
+        if CS == 16 and torch.is_grad_enabled():       # (the CS = 16 scan has no MFMA backward: with grad enabled the layer stays one piece)
             return None
         if not linear3_applies(self.wq, self.wk, self.wv, x) or not linear3_applies(self.wo, self.wo, self.wo, x):
             return None                    # (DTensor parameters, autocast: the pre-pass's raw GEMMs would not be the modules' arithmetic)
         NC = L // CS
         G = self._group_size(NC)
-        if self.pipeline_parts_auto:
-            n = max(n, min(8, -(-NC // G) // 40))
-        if -(-NC // G) < 8:                    # (rounds 5 / 6: a scan of fewer than eight checkpoint groups runs as one piece)
-            return None
-        n = min(n, -(-NC // G) // 2)           # at least two checkpoint groups per part on average
+        if CS == 16:
+            # sampling: ONE checkpoint group for the whole sequence, so the parts are cut at multiples of a step quantum instead (the
+            # CS = 16 scan continues from any step); `unit` takes G's place in the plan, the scan still gets the real G
+            unit = pipeline.CS16_QUANTUM
+            if NC < pipeline.CS16_MIN_STEPS:
+                return None
+            if self.pipeline_parts_auto:
+                n = pipeline.CS16_PARTS
+            n = min(n, -(-NC // unit) // 3)        # at least three quanta per part on average (9 s: 4 parts beat 6, profiles/r7_cs16_parts_*)
+        else:
+            unit = G
+            if self.pipeline_parts_auto:
+                n = max(n, min(8, -(-NC // G) // 40))
+            if -(-NC // G) < 8:                    # (rounds 5 / 6: a scan of fewer than eight checkpoint groups runs as one piece)
+                return None
+            n = min(n, -(-NC // G) // 2)           # at least two checkpoint groups per part on average
         import test_time_training as ext
         if ext.resolved_impl(x.shape[0], self.num_heads, NC, CS, self.head_dim, G, torch.bfloat16, mlp=True, backward=False) != "mfma":
             return None
-        key = ("parts", n, meta.num_chunks, meta.text_length, meta.seq_text_length, meta.init_offset, meta.base_offset, L, reverse)
+        key = ("parts", n, unit, meta.num_chunks, meta.text_length, meta.seq_text_length, meta.init_offset, meta.base_offset, L, reverse)
         hit = self._perm_cache.get(key)
         if hit is None:
-            from ttt_amd.models.ssm.pipeline import plan_parts
             seq = scene_permutation(meta, L) if meta.is_multiscene else None      # scan position -> index in the (reversed) sequence
             if reverse:
                 r = reversal_map(meta, L)
                 seq = r if seq is None else r[seq]                                 # -> token of the input sequence (= the maps' src)
-            hit = self._perm_cache[key] = plan_parts(seq, L, CS, G, n)
+            hit = self._perm_cache[key] = pipeline.plan_parts(seq, L, CS, unit, n)
         return hit
 
     def _eta_rows(self, x, rev, meta, L):

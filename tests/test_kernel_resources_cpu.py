@@ -46,9 +46,11 @@ def test_recompute_kernel_does_not_spill():
 
 def test_cluster_sweep_spill_budget():
     res = kernel_resources("ttt_mfma_bwd4.hip")
-    # the production instantiation: no stamps, bf16 records, owner overlap, derivers on waves 2 - 3 (round 6: the derivers carry no W1
-    # tiles any more - 95 spilled dwords where rounds 4 / 5 had 114 - 138)
-    k = next(k for k in res if "mlp_bwd_cluster4_kernel" in k and "Lb0ELb1ELb1ELi2ELb1E" in k)
+    # exactly the two instantiations the host launches (with / without stage stamps): a variant that comes back shows up here
+    assert sum("mlp_bwd_cluster4_kernel" in k for k in res) == 2, list(res)
+    # the production instantiation: no stamps (round 6: the derivers carry no W1 tiles any more - 95 spilled dwords where rounds
+    # 4 / 5 had 114 - 138)
+    k = next(k for k in res if "mlp_bwd_cluster4_kernelILb0EE" in k)
     v = res[k]
     assert v["vgpr_count"] <= 256, v
     assert v["vgpr_spill_count"] <= 130, f"the cluster sweep spills {v['vgpr_spill_count']} dwords (budget 130; measured good: 95)"
@@ -60,12 +62,14 @@ def test_forward_scan_does_not_spill():
     """The 8-wave forward scan (csrc/ttt_mfma2.hip) runs two waves per SIMD at <= 256 registers and is spill-free by construction
     (opaque per-step lane indices, pinned gelu'); round 5 saw it go from 232 registers / 0 spills to 256 / 76 spilled dwords when a
     final-state store behind the step loop formed its addresses from the function-scope lane index - fixed with an opaque index of
-    its own, pinned here (production instantiation: no stamps, half-chunk swap)."""
+    its own, pinned here (production instantiation: no stamps)."""
     res = kernel_resources("ttt_mfma2.hip")
-    k = next(k for k in res if "mlp_scan8_kernel" in k and "Lb0ELb1E" in k)
+    # exactly the instantiations the host launches (with / without stamps, of each form): a variant that comes back shows up here
+    assert sum("mlp_scan8_kernel" in k for k in res) == 2 and sum("mlp_scan_pair_kernel" in k for k in res) == 2, list(res)
+    k = next(k for k in res if "mlp_scan8_kernelILb0EE" in k)
     v = res[k]
     assert v["vgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0 and v["vgpr_count"] <= 256, (k, v)
     # round 6: the pair form (role A = the same chain, role B = the output path, one kernel) - the same budget
-    k = next(k for k in res if "mlp_scan_pair_kernel" in k and "Lb0E" in k)
+    k = next(k for k in res if "mlp_scan_pair_kernelILb0EE" in k)
     v = res[k]
     assert v["vgpr_spill_count"] == 0 and v["private_segment_fixed_size"] == 0 and v["vgpr_count"] <= 256, (k, v)

@@ -2,30 +2,42 @@
 
     python tools/compare_isa.py <git-commit>            # that commit's csrc/ against the working tree
 
-Compiles every translation unit of ttt-video-dit_amd/csrc to gfx950 assembly (device only) in both trees and compares
-the instruction streams kernel by kernel (labels normalised, comments dropped).  Used to show that a refactor - e.g.
-adding an opt-in template variant next to a kernel that has been validated on the hardware - leaves the default-dispatched
-code bit-for-bit alone when no GPU is at hand to re-run the parity tests.
+Compiles every translation unit of ttt-video-dit_amd/csrc (the *.hip files present in both trees, with the flags of csrc/build.sh) to
+gfx950 assembly (device only) in both trees and compares the instruction streams kernel by kernel (labels normalised, comments
+dropped).  Used to show that a refactor - e.g. dropping a template parameter that has one instantiation left - leaves the code of
+every kernel bit-for-bit alone when no GPU is at hand to re-run the parity tests.  A kernel whose stream is found under another name
+(its template arguments changed) is reported as "identical, now named ..."; exit status 1 if any kernel changed or disappeared.
 """
+import glob
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ["ttt_generic", "ttt_mfma", "ttt_mfma2", "ttt_mfma16", "ttt_mfma_bwd", "ttt_mfma_bwd2", "ttt_prepost", "attn_fwd", "attn_bwd", "attn_pre"]
+CSRC = os.path.join("ttt-video-dit_amd", "csrc")
 
 
-def asm(src_dir, unit, out):
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", unit + ".hip", "-o", out],
+def build_flags():
+    """FLAGS of csrc/build.sh, so that both trees are compiled the way the library is."""
+    m = re.search(r'^FLAGS="([^"]*)"', open(os.path.join(ROOT, CSRC, "build.sh")).read(), flags=re.M)
+    return m.group(1).split()
+
+
+def asm(src_dir, unit, out, flags):
+    subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-S", "--cuda-device-only", unit + ".hip", "-o", out],
                    cwd=src_dir, stderr=subprocess.DEVNULL, check=True)
+    text = open(out).read()
+    functions = set(re.findall(r"^\s*\.type\s+(_Z\w+),@function", text, flags=re.M))      # (not the __device__ variables)
     kernels, cur = {}, None
-    for line in open(out).read().split("\n"):
+    for line in text.split("\n"):
         m = re.match(r"^(_Z\w+):", line)
         if m:
-            cur = m.group(1)
-            kernels[cur] = []
+            cur = m.group(1) if m.group(1) in functions else None
+            if cur is not None:
+                kernels[cur] = []
         elif cur is not None:
             if "s_endpgm" in line:
                 cur = None
@@ -38,15 +50,20 @@ def asm(src_dir, unit, out):
 
 def main():
     commit = sys.argv[1]
+    flags = build_flags()
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.run(f"git -C {ROOT} archive {commit} ttt-video-dit_amd/csrc include | tar -x -C {tmp}", shell=True, check=True)
-        old_dir, new_dir = os.path.join(tmp, "ttt-video-dit_amd", "csrc"), os.path.join(ROOT, "ttt-video-dit_amd", "csrc")
+        subprocess.run(f"git -C {ROOT} archive {commit} {CSRC} include | tar -x -C {tmp}", shell=True, check=True)
+        old_dir, new_dir = os.path.join(tmp, CSRC), os.path.join(ROOT, CSRC)
+        names = lambda d: {os.path.basename(f)[:-4] for f in glob.glob(os.path.join(d, "*.hip"))}
+        units = sorted(names(old_dir) & names(new_dir))
+        for unit in sorted(names(old_dir) ^ names(new_dir)):
+            print(f"{unit}: not in both trees, skipped")
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            jobs = {(unit, d): pool.submit(asm, d, unit, os.path.join(tmp, f"{unit}.{tag}.s"), flags)
+                    for unit in units for tag, d in (("a", old_dir), ("b", new_dir))}
         changed = 0
-        for unit in UNITS:
-            if not os.path.exists(os.path.join(old_dir, unit + ".hip")):
-                print(f"{unit}: not in {commit}")
-                continue
-            a, b = asm(old_dir, unit, os.path.join(tmp, "a.s")), asm(new_dir, unit, os.path.join(tmp, "b.s"))
+        for unit in units:
+            a, b = jobs[unit, old_dir].result(), jobs[unit, new_dir].result()
             by_code = {tuple(v): k for k, v in b.items()}
             for k, v in a.items():
                 if k in b and b[k] == v:

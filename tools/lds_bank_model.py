@@ -62,7 +62,7 @@ class Layout:
 
     def at(self, base, r, col, nbytes=8):
         if self.half_swap and nbytes < 16:
-            # csrc/ttt_mfma2.hip template parameter SW (sw_x): padded rows kept; the two 8-byte units of a 16-byte chunk swapped
+            # the half-chunk swap of csrc/ttt_mfma2.hip (sw_x): padded rows kept; the two 8-byte units of a 16-byte chunk swapped
             # in rows with bit 3 ^ bit 4 set (a 16-byte access keeps its address and swaps its halves in registers)
             return base + 2 * (r * self.ts + (col ^ (4 * (((r >> 3) ^ (r >> 4)) & 1))))
         if not self.swizzle:

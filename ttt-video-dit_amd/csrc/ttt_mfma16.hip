@@ -34,6 +34,7 @@
 // P6 at that time, hence the third buffer).
 #include "ttt_mfma.h"
 #include "ttt_mfma_dev.h"
+#include "ttt_dpp.h"
 #include "ttt_mfma_int.h"
 #define TTT_WV_FN __device__ __forceinline__
 #include "ttt_lin16_body.h"
@@ -93,18 +94,6 @@ __device__ __forceinline__ bf16x4 tr4(const __bf16* img, int stride, int row0, i
     return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + (row0 + 4 * g + (i >> 2)) * stride + col0 + 4 * (i & 3)));
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum16(float v) {
-    v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f<0x141>(v);     // row_half_mirror
-    v += dpp_f<0x140>(v);     // row_mirror
-    return v;
-}
-
 // (The hand-placed 8-wave kernel of round 1, mlp_scan16_kernel, lost its round-2 A/B against the backend-templated body of
 // ttt_mlp16_body.h - 3.006 vs 2.924 ms per scan at NH = 48, NC = 1128, batch 2 - and was removed; the body is also what the CPU
 // suite runs on the wave emulator.)
@@ -138,7 +127,7 @@ struct DeviceWave {
         typedef __attribute__((address_space(3))) bf16x4 lds_b4;
         return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(base + byte_addr));
     }
-    __device__ __forceinline__ float sum16(float v) const { return v16::sum16(v); }
+    __device__ __forceinline__ float sum16(float v) const { return ttt::sum16(v); }
     __device__ __forceinline__ float xor_add(float v, int mask) const { return v + __shfl_xor(v, mask, 64); }
 };
 

@@ -34,6 +34,7 @@
 // Q/K/V of step i+1 are fetched into registers at the top of step i.
 #include "ttt_mfma.h"
 #include "ttt_mfma_dev.h"
+#include "ttt_dpp.h"
 #include "ttt_mfma_int.h"
 #include "once_per_device.h"
 
@@ -113,53 +114,19 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_srd(const void* base, siz
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-// ---- DPP reductions over the 8 lanes of an owner group ---------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum8(float v) {
-    v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f<0x141>(v);     // row_half_mirror
-    return v;
-}
-
-// ---- transposed LDS read: operand fragment (outer = column, contract = row) of a row-major bf16 image ----
-// rows r0..r0+3 and r1..r1+3 (8 k-slots), 32 outer columns starting at col0; `img` row stride = stride elems.
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int stride, int r0, int r1, int col0, int l) {
-    const int i = l & 15, g1 = (l >> 4) & 1;
-    const int off = (i >> 2) * stride + col0 + 16 * g1 + 4 * (i & 3);
-    // NB: no per-element __builtin_bit_cast on vector elements (it reads element 0 for every index): use the
-    // bf16-typed builtin and concatenate whole vectors.
-    typedef __attribute__((address_space(3))) bf16x4 lds_b4;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r0 * stride + off));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r1 * stride + off));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// same, in the pi k-slot order of an in-place C tile fragment s of the 32-row block starting at row0
-__device__ __forceinline__ bf16x8 tr_frag_pi(const __bf16* img, int stride, int row0, int s, int col0, int l) {
-    const int h = l >> 5;
-    return tr_frag(img, stride, row0 + 16 * s + 4 * h, row0 + 16 * s + 8 + 4 * h, col0, l);
-}
-
-// ---- half-chunk swap (template parameter SW of the scan) ------------------------------------------------------------------
+// ---- half-chunk swap of the LDS tile rows --------------------------------------------------------------------------------------
 // With the 144-byte row stride every 8-byte access that walks ROWS at a fixed column (pi_read, st_image) is a 2-way bank
 // conflict: rows r and r + 16 (reads: 32 lanes over 64 banks) or r and r + 8 (writes: 16 lanes over 32 banks) meet in the same
-// banks (tools/lds_bank_model.py: 1 280 of a step's 7 576 LDS passes).  Under SW the two 8-byte units of every 16-byte chunk
+// banks (tools/lds_bank_model.py: 1 280 of a step's 7 576 LDS passes).  So the two 8-byte units of every 16-byte chunk
 // of a tile row are stored swapped in rows with  x(r) = bit 3 ^ bit 4 of r  = 1, which sends the colliding rows to
 // different banks.  The price is address selection only: for the row walkers x is a lane constant folded into `h`, for the
 // transposed reads it is a compile-time constant per instruction, and the 16-byte accessors (tile parking, the owners' rows)
-// swap the halves of their value in registers (4 v_cndmask).  The data are the same: SW on / off give identical bits.
+// swap the halves of their value in registers (4 v_cndmask).  (Round-5 A/B against unswapped rows: 6.06 against 6.22 ms at NC = 804,
+// 2.14 against 2.19 at NC = 282, identical bits, profiles/r4m_*.)
 __device__ __forceinline__ int sw_x(int r) { return ((r >> 3) ^ (r >> 4)) & 1; }
-template <bool SW>
-__device__ __forceinline__ uint4 sw16(uint4 v, int x) {
-    if (!SW) return v;
-    return x ? uint4{v.z, v.w, v.x, v.y} : v;
-}
-template <bool SW>
+__device__ __forceinline__ uint4 sw16(uint4 v, int x) { return x ? uint4{v.z, v.w, v.x, v.y} : v; }
+// tr_frag_pi (ttt_mfma_dev.h) of a swapped image
 __device__ __forceinline__ bf16x8 tr_frag_pi_sw(const __bf16* img, int stride, int row0, int s, int col0, int l) {
-    if (!SW) return tr_frag_pi(img, stride, row0, s, col0, l);
     // rows row0 + 16 s + 4 h + (0 | 8) + (i >> 2), row0 a multiple of 32: bit 4 = s, bit 3 = (0 | 1)  ->  x = s for the
     // first read, s ^ 1 for the second; the lane's unit (i & 3) of its 16-column group flips its low bit when x = 1
     const int h = l >> 5, i = l & 15, g1 = (l >> 4) & 1;
@@ -171,19 +138,13 @@ __device__ __forceinline__ bf16x8 tr_frag_pi_sw(const __bf16* img, int stride, i
     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + (r0 + 8) * stride + ((s & 1) ? off0 : off1)));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-template <bool SW>
 __device__ __forceinline__ void load8_bf16_sw(const __bf16* p, int x, float (&o)[8]) {
-    const uint4 raw = sw16<SW>(*reinterpret_cast<const uint4*>(p), x);
+    const uint4 raw = sw16(*reinterpret_cast<const uint4*>(p), x);
     const bf16x8 a = __builtin_bit_cast(bf16x8, raw);
 #pragma unroll
     for (int j = 0; j < 8; ++j) o[j] = (float)a[j];
 }
 
-__device__ __forceinline__ void load8_bf16(const __bf16* p, float (&o)[8]) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)a[j];
-}
 __device__ __forceinline__ void load8_f32(const float* p, float (&o)[8]) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
@@ -238,7 +199,7 @@ __device__ __forceinline__ void gelu_fwd_grad_tile_pk(f32x16& z, float b, f32x16
 // PAIR = false: the whole step in one workgroup (the round-2 .. round-5 kernel).  PAIR = true: role A of the pair form - the same
 // chain A1 .. C with the same instructions; K / V / eta are double-buffered by step parity (without the phases of the output path no
 // window is left in which the single buffers are free), the output path is replaced by the record of the updated state.
-template <bool DBG, bool SW, bool PAIR>
+template <bool DBG, bool PAIR>
 __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams& q, char* smem, const int bh) {
     __bf16* const Kt2 = reinterpret_cast<__bf16*>(smem + (PAIR ? LA_K : L_K));
     __bf16* const Vt2 = reinterpret_cast<__bf16*>(smem + (PAIR ? LA_V : L_V));
@@ -319,8 +280,8 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
         pfK = *reinterpret_cast<const uint4*>(p.XK + off);
         pfV = *reinterpret_cast<const uint4*>(p.XV + off);
         pfE = reinterpret_cast<const unsigned short*>(p.eta)[tile0 * 64 + (tid & 63)];
-        *reinterpret_cast<uint4*>(Kt + prow * TS + pcol) = sw16<SW>(pfK, sw_x(prow));
-        *reinterpret_cast<uint4*>(Vt + prow * TS + pcol) = sw16<SW>(pfV, sw_x(prow));
+        *reinterpret_cast<uint4*>(Kt + prow * TS + pcol) = sw16(pfK, sw_x(prow));
+        *reinterpret_cast<uint4*>(Vt + prow * TS + pcol) = sw16(pfV, sw_x(prow));
         unsigned pfEu = pfE;
         asm volatile("" : "+v"(pfEu));     // every wave consumes its load HERE (left to the compiler the conversion sinks into the branch below,
                                           // the register stays pending in the other waves, and its pairing with b1v in A1 waits vmcnt(0) there)
@@ -349,8 +310,8 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
         const int tid = tid_op;
         const int ot = tid >> 3, of0 = 8 * (tid & 7);
         const int prow = tid >> 3, pcol = (tid & 7) * 8;
-        const int hs = SW ? (h ^ sw_x(c)) : h;                // the row walkers' half selector (rows = 32 k + c): see sw_x
-        const int xo = SW ? sw_x(ot) : 0;                     // the 16-byte accessors' swap (row ot == prow)
+        const int hs = h ^ sw_x(c);                           // the row walkers' half selector (rows = 32 k + c): see sw_x
+        const int xo = sw_x(ot);                              // the 16-byte accessors' swap (row ot == prow)
         if (PAIR) {                                           // tiles of this step: the buffers of its parity
             Kt = Kt2 + (i & 1) * TILE_ELEMS;
             Vt = Vt2 + (i & 1) * TILE_ELEMS;
@@ -435,7 +396,7 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
             }
         }
         if (DBG && p.dump && blockIdx.x == 0 && i == 0)
-            for (int e = tid; e < 256 * 64; e += NT2) p.dump[e] = (float)X2img[(e >> 6) * TS + ((e & 63) ^ (SW ? 4 * sw_x(e >> 6) : 0))];
+            for (int e = tid; e < 256 * 64; e += NT2) p.dump[e] = (float)X2img[(e >> 6) * TS + ((e & 63) ^ 4 * sw_x(e >> 6))];
 
         // ================= A2: partial Z2^T[Fp, t] over the hidden slice ==========================
         {
@@ -449,13 +410,13 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
                 f32x16 P = zero16();
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    P = mma(W2F[0][s], tr_frag_pi_sw<SW>(X2img, TS, nO, s, 32 * ti, l), P);
-                    P = mma(W2F[1][s], tr_frag_pi_sw<SW>(X2img, TS, nX, s, 32 * ti, l), P);
+                    P = mma(W2F[0][s], tr_frag_pi_sw(X2img, TS, nO, s, 32 * ti, l), P);
+                    P = mma(W2F[1][s], tr_frag_pi_sw(X2img, TS, nX, s, 32 * ti, l), P);
                 }
                 write_partial2(red + (size_t)w * 64 * PS, P, ti, pp, h, c);
             }
         }
-        if (!PAIR) *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16<SW>(pfQ, xo);   // Q of this step (read only after B2)
+        if (!PAIR) *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16(pfQ, xo);   // Q of this step (read only after B2)
         TTT_STAMP2(1)
         if (PAIR) asm volatile("s_waitcnt vmcnt(0) ; drain: the record of step i - 1 is in memory before its flag is stored" ::: "memory");
         __syncthreads();              // B1: partials visible
@@ -482,8 +443,8 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
             for (int j = 0; j < 8; ++j) { const float d = z[j] - mu; v += d * d; }
             const float rstd = __builtin_amdgcn_rsqf(sum8(v) * (1.0f / 64.0f) + p.eps);
             if (DBG && p.dump && blockIdx.x == 0 && i == 0 && (tid & 7) == 0) { p.dump[60000 + ot] = mu; p.dump[60064 + ot] = rstd; }
-            load8_bf16_sw<SW>(Kt + ot * TS + of0, xo, kk);
-            load8_bf16_sw<SW>(Vt + ot * TS + of0, xo, vv);
+            load8_bf16_sw(Kt + ot * TS + of0, xo, kk);
+            load8_bf16_sw(Vt + ot * TS + of0, xo, vv);
             float s1 = 0.f, s2 = 0.f, gx[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -499,20 +460,20 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
             bf16x8 o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (__bf16)((64.0f * gx[j] - s1 - z[j] * s2) * sc);
-            *reinterpret_cast<uint4*>(Gs + ot * TS + of0) = sw16<SW>(__builtin_bit_cast(uint4, o), xo);
+            *reinterpret_cast<uint4*>(Gs + ot * TS + of0) = sw16(__builtin_bit_cast(uint4, o), xo);
         }
         TTT_STAMP2(2)
         __syncthreads();              // B2: Gs visible
         TTT_STAMP2(10)
         if (DBG && p.dump && blockIdx.x == 0 && i == 0)
-            for (int e = tid; e < 64 * 64; e += NT2) p.dump[20480 + e] = (float)Gs[(e >> 6) * TS + ((e & 63) ^ (SW ? 4 * sw_x(e >> 6) : 0))];
+            for (int e = tid; e < 64 * 64; e += NT2) p.dump[20480 + e] = (float)Gs[(e >> 6) * TS + ((e & 63) ^ 4 * sw_x(e >> 6))];
 
         // pair form: the next step's tiles, requested behind B0, go to the other parity's buffers (last read in phase C of step i - 1) HERE -
         // behind A2 the wait for them cost 0.5 k cycles per step (stamps of profiles/r6t_* / r6v_*), now they have had A2 and P3 to arrive
         if (PAIR && more) {           // the other parity's buffers: last read in phase C of step i - 1
             const int nb = (i & 1) ^ 1;
-            *reinterpret_cast<uint4*>(Kt2 + nb * TILE_ELEMS + prow * TS + pcol) = sw16<SW>(pfK, xo);
-            *reinterpret_cast<uint4*>(Vt2 + nb * TILE_ELEMS + prow * TS + pcol) = sw16<SW>(pfV, xo);
+            *reinterpret_cast<uint4*>(Kt2 + nb * TILE_ELEMS + prow * TS + pcol) = sw16(pfK, xo);
+            *reinterpret_cast<uint4*>(Vt2 + nb * TILE_ELEMS + prow * TS + pcol) = sw16(pfV, xo);
             unsigned pfEu = pfE;
             asm volatile("" : "+v"(pfEu));
             const float pfEf = __builtin_bit_cast(float, pfEu << 16);
@@ -556,7 +517,7 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
 #pragma unroll
                 for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-                    for (int s = 0; s < 2; ++s) acc = mma(ONES, tr_frag_pi_sw<SW>(Gs, TS, 32 * ti, s, fO, l), acc);
+                    for (int s = 0; s < 2; ++s) acc = mma(ONES, tr_frag_pi_sw(Gs, TS, 32 * ti, s, fO, l), acc);
                 b2v += acc[0];
             }
             // f5 + W2^T update.  Gs^T fragments (outer=f, k=t) by transposed reads: own half of f (also f5's B
@@ -566,12 +527,12 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
             for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const bf16x8 gO = tr_frag_pi_sw<SW>(Gs, TS, 32 * ti, s, fO, l);
+                    const bf16x8 gO = tr_frag_pi_sw(Gs, TS, 32 * ti, s, fO, l);
                     const bf16x8 xO = pi_read(X2img + (nO + c) * TS, 32 * ti, s, hs);
                     W2t[0] = mma(xO, gO, W2t[0]);                                                  // f5, own hidden half
                     W2t[1] = mma(pi_read(X2img + (nX + c) * TS, 32 * ti, s, hs), gO, W2t[1]);       // f5, partner's half
                     W2Tt[0] = mma(gO, xO, W2Tt[0]);
-                    W2Tt[1] = mma(tr_frag_pi_sw<SW>(Gs, TS, 32 * ti, s, fX, l), xO, W2Tt[1]);
+                    W2Tt[1] = mma(tr_frag_pi_sw(Gs, TS, 32 * ti, s, fX, l), xO, W2Tt[1]);
                 }
             if constexpr (PAIR) {     // W2' is final: its half of the record leaves under f3 / f4
                 const int vo = (wv * 4) * 1024 + l * 16;
@@ -604,8 +565,8 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const bf16x8 gz = pack(gx, s);           // (outer=n, k=t)
-                    W1t[0] = mma(tr_frag_pi_sw<SW>(Kt, TS, 32 * ti, s, 0, l), gz, W1t[0]);
-                    W1t[1] = mma(tr_frag_pi_sw<SW>(Kt, TS, 32 * ti, s, 32, l), gz, W1t[1]);
+                    W1t[0] = mma(tr_frag_pi_sw(Kt, TS, 32 * ti, s, 0, l), gz, W1t[0]);
+                    W1t[1] = mma(tr_frag_pi_sw(Kt, TS, 32 * ti, s, 32, l), gz, W1t[1]);
                 }
             }
             b1v += xor_add(sb, 32);   // b1' = b1 - sum_t eta gZ1
@@ -720,8 +681,8 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
             }
         }
         if (more) {                   // next step's K, V, eta (their last readers finished before B3)
-            *reinterpret_cast<uint4*>(Kt + prow * TS + pcol) = sw16<SW>(pfK, xo);
-            *reinterpret_cast<uint4*>(Vt + prow * TS + pcol) = sw16<SW>(pfV, xo);
+            *reinterpret_cast<uint4*>(Kt + prow * TS + pcol) = sw16(pfK, xo);
+            *reinterpret_cast<uint4*>(Vt + prow * TS + pcol) = sw16(pfV, xo);
             unsigned pfEu = pfE;
             asm volatile("" : "+v"(pfEu));     // every wave consumes its load HERE (left to the compiler the conversion sinks into the branch below,
                                               // the register stays pending in the other waves, and its pairing with b1v in A1 waits vmcnt(0) there)
@@ -748,7 +709,7 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float d = z[j] - mu; v += d * d; }
             const float rstd = __builtin_amdgcn_rsqf(sum8(v) * (1.0f / 64.0f) + p.eps);
-            load8_bf16_sw<SW>(Qt + ot * TS + of0, xo, q);
+            load8_bf16_sw(Qt + ot * TS + of0, xo, q);
             bf16x8 o;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = (__bf16)(q[j] + gamL[of0 + j] * ((z[j] - mu) * rstd) + betL[of0 + j]);
@@ -781,10 +742,10 @@ __device__ __forceinline__ void scan8_body(const ScanParams& p, const PairParams
     }
 }
 
-template <bool DBG, bool SW>
+template <bool DBG>
 __global__ __launch_bounds__(NT2) void mlp_scan8_kernel(ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    scan8_body<DBG, SW, false>(p, PairParams{}, smem, (int)blockIdx.x);
+    scan8_body<DBG, false>(p, PairParams{}, smem, (int)blockIdx.x);
 }
 
 // ---- role B of the pair form: the output path of every step, from the records role A publishes -----------------------------------
@@ -796,7 +757,7 @@ __global__ __launch_bounds__(NT2) void mlp_scan8_kernel(ScanParams p) {
         p.dbg[k] += _t - t_last;                                                   \
         t_last = _t;                                                               \
     }
-template <bool DBG, bool SW>
+template <bool DBG>
 __device__ __forceinline__ void scan8_output_role(const ScanParams& p, const PairParams& q, char* smem, const int bh) {
     __bf16* Qt = reinterpret_cast<__bf16*>(smem + LB_Q);
     char* exch = smem + LB_EX;
@@ -827,7 +788,7 @@ __device__ __forceinline__ void scan8_output_role(const ScanParams& p, const Pai
     {
         const int prow = tid >> 3, pcol = (tid & 7) * 8;
         qcur = *reinterpret_cast<const uint4*>(p.XQ + tile0 * 4096 + (size_t)prow * 64 + pcol);
-        *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16<SW>(qcur, SW ? sw_x(prow) : 0);
+        *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16(qcur, sw_x(prow));
     }
     qnext = qcur;
     bool gave_up = false;
@@ -843,8 +804,8 @@ __device__ __forceinline__ void scan8_output_role(const ScanParams& p, const Pai
         const int tid = tid_op;
         const int ot = tid >> 3, of0 = 8 * (tid & 7);
         const int prow = tid >> 3, pcol = (tid & 7) * 8;
-        const int hs = SW ? (h ^ sw_x(c)) : h;
-        const int xo = SW ? sw_x(ot) : 0;
+        const int hs = h ^ sw_x(c);
+        const int xo = sw_x(ot);
         if (more) qnext = *reinterpret_cast<const uint4*>(p.XQ + (tile + 1) * 4096 + (size_t)prow * 64 + pcol);
 
         // ---- wait for record i (every wave polls for itself: one lane, bounded by the wall clock) ---------------------------
@@ -925,7 +886,7 @@ __device__ __forceinline__ void scan8_output_role(const ScanParams& p, const Pai
             }
             write_partial2(red + (size_t)w * 64 * PS, P, ti, pp, h, c);
         }
-        if (more) *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16<SW>(qnext, xo);       // (its readers, f6 of this step, are behind B4)
+        if (more) *reinterpret_cast<uint4*>(Qt + prow * TS + pcol) = sw16(qnext, xo);       // (its readers, f6 of this step, are behind B4)
         asm volatile("s_waitcnt vmcnt(0) ; every load of record i has landed before its slot is released" ::: "memory");
         TTT_STAMP2B(6)
         __syncthreads();              // B5
@@ -968,15 +929,15 @@ template <bool DBG>
 __global__ __launch_bounds__(NT2) void mlp_scan_pair_kernel(ScanParams p, PairParams q) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = (int)blockIdx.x;
-    if (b < q.nbh) scan8_body<DBG, true, true>(p, q, smem, b);
-    else if (b >= q.nbh8 && !q.fault) scan8_output_role<DBG, true>(p, q, smem, b - q.nbh8);
+    if (b < q.nbh) scan8_body<DBG, true>(p, q, smem, b);
+    else if (b >= q.nbh8 && !q.fault) scan8_output_role<DBG>(p, q, smem, b - q.nbh8);
 }
 
 static void set_attr_once() {
     static ttt::OncePerDevice done;
     done.run([&] {
-        (void)hipFuncSetAttribute((const void*)mlp_scan8_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_V2);
-        (void)hipFuncSetAttribute((const void*)mlp_scan8_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_V2);
+        (void)hipFuncSetAttribute((const void*)mlp_scan8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_V2);
+        (void)hipFuncSetAttribute((const void*)mlp_scan8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_V2);
         (void)hipFuncSetAttribute((const void*)mlp_scan_pair_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_PAIR);
         (void)hipFuncSetAttribute((const void*)mlp_scan_pair_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_PAIR);
     });
@@ -986,8 +947,6 @@ static void set_attr_once() {
 
 static float* g_dump = nullptr;
 void set_debug_dump(float* buf) { g_dump = buf; }
-// (the half-chunk swap of the LDS tile rows - template parameter SW, sw_x above - is always on since round 5: 6.06 against 6.22 ms at
-// NC = 804, 2.14 against 2.19 at NC = 282, identical bits, profiles/r4m_*)
 static int g_scan_pair = 1;           // 1 (default, round 6): the CS = 64 forward scan as a pair of workgroups per (b,h); 0 = one workgroup
 void set_debug_scan_pair(int v) { g_scan_pair = v; }
 static int g_scan_fault = 0;          // DEBUG fault injection: role B never runs - role A must give up loudly
@@ -1017,8 +976,8 @@ void launch_scan_forward_v2(const ScanParams& p0, int n_bh, void* ws, unsigned l
         else hipLaunchKernelGGL((v2::mlp_scan_pair_kernel<false>), dim3(n_bh8 + n_bh), dim3(v2::NT2), v2::LDS_PAIR, s, p, q);
         return;
     }
-    if (dbg_build) hipLaunchKernelGGL((v2::mlp_scan8_kernel<true, true>), dim3(n_bh), dim3(v2::NT2), v2::LDS_V2, s, p);
-    else hipLaunchKernelGGL((v2::mlp_scan8_kernel<false, true>), dim3(n_bh), dim3(v2::NT2), v2::LDS_V2, s, p);
+    if (dbg_build) hipLaunchKernelGGL((v2::mlp_scan8_kernel<true>), dim3(n_bh), dim3(v2::NT2), v2::LDS_V2, s, p);
+    else hipLaunchKernelGGL((v2::mlp_scan8_kernel<false>), dim3(n_bh), dim3(v2::NT2), v2::LDS_V2, s, p);
 }
 
 }  // namespace mfma

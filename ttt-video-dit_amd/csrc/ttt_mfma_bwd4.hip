@@ -26,10 +26,10 @@
 // Workgroup = 8 waves (wave w on SIMD w % 4):
 //   waves 0, 1  COMPUTE: wave pp owns the 32 hidden units [64 cq + 32 pp, +32): the carried dW1 / dW2 (both orientations) /
 //               db1 tiles and every MFMA of the gradient chain;
-//   waves 2, 3, 6, 7  OWNERS (256 threads = 64 tokens x 4 lanes x 16 features): staging of the next step's K / gZ2 / Q / eta
+//   waves 4 - 7  OWNERS (256 threads = 64 tokens x 4 lanes x 16 features): staging of the next step's K / gZ2 / Q / eta
 //               tiles into LDS (double-buffered), the output-LayerNorm backward of the next step, the hand-over (flag, poll,
 //               record reads), the fused-LN / L2 backward-of-backward -> dZ2, dV, d(eta), dgamma / dbeta, L2 prefetch touches;
-//   waves 4, 5  DERIVERS (round 3; beside the compute waves on SIMDs 0 / 1, which idle during the hand-over): wave pp loads the
+//   waves 2, 3  DERIVERS (round 3; on SIMDs 2 / 3 beside two of the owner waves, see FIRST_DERIVER below): wave 2 + pp loads the
 //               slice's Z1 / Z1b fragments (16 KiB per step and CU where round 2's owners DMA-staged 80 KiB of register
 //               images), re-derives X2, gelu', gelu'', X2b, gelu'(Z1b), gX2, gZ1, M and the second orientations, REVERSES the
 //               state update to obtain the per-step W1 / W2 (fp32, re-anchored at every forward checkpoint) and writes exactly
@@ -68,13 +68,11 @@ using namespace ttt::mfma::b2;
 using namespace ttt::mfma::s4;
 
 constexpr int NTC = 512;                                  // 2 compute waves + 4 owner waves + 2 deriver waves
-// Wave roles.  Waves are placed on the CU's four SIMDs round-robin (wave w on SIMD w % 4): the compute waves 0, 1 and the
-// deriver waves DW0, DW0 + 1 = 4, 5 share SIMDs 0 / 1 - the compute waves idle there during the hand-over, which is when the
-// derivers do most of their (VALU-heavy) work -, the owner waves 2, 3, 6, 7 have SIMDs 2 / 3 to themselves: their hand-over
-// chain (poll, record reads, LayerNorm backward-of-backward) is the critical path of a step.
-// (round 4: DW0 is a template parameter of the kernel - 4 as above, or 2: the derivers on SIMDs 2 / 3 beside two of the owner
-// waves, the other two owner waves beside the compute waves - the stage stamps of profiles/r4b show the Bb .. Bc phase bounded by
-// the derivers' reverse_step (12.5 k cycles) with the owners finished after 8.2 k and the compute waves after 5.1 k)
+// Wave roles.  Waves are placed on the CU's four SIMDs round-robin (wave w on SIMD w % 4): the deriver waves FIRST_DERIVER, + 1 = 2, 3
+// share SIMDs 2 / 3 with the owner waves 6, 7, the owner waves 4, 5 share SIMDs 0 / 1 with the compute waves 0, 1.  (Round-4 A/B
+// against derivers on waves 4, 5 beside the compute waves: 11.48 - 11.62 against 11.79 - 11.94 ms per backward at NC = 804, profiles/r4b.)
+constexpr int FIRST_DERIVER = 2;
+constexpr int FIRST_OWNER = 4;                            // (it polls the partner flags)
 constexpr int TILE_B = TILE_ELEMS * 2;                    // 9216 bytes: one padded [64][64] bf16 tile
 constexpr int L_K = 0;                                    // K   [2][t][f]  (by step parity)
 constexpr int L_G = L_K + 2 * TILE_B;                     // gZ2 [2][t][f]
@@ -103,15 +101,6 @@ static_assert(2 * TILE_B >= 256 * 16 * 4, "the final dgamma / dbeta reduction re
 
 __device__ unsigned g_fast_count4 = 0;       // DEBUG statistic: cluster workgroups that proved same-XCD placement and switched to plain records
 
-template <int CTRL>
-__device__ __forceinline__ float dppq(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum4(float v) {          // over the 4 adjacent lanes that share an owner token
-    v += dppq<0xB1>(v);
-    v += dppq<0x4E>(v);
-    return v;
-}
 __device__ __forceinline__ void ld16f(__amdgpu_buffer_rsrc_t r, int voff, int soff, float (&o)[16]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -175,32 +164,26 @@ struct DeriverBackend {
     }
 };
 
+// The owners' partner-independent arithmetic runs while the partner records are in flight: this statement "produces" the records as
+// far as the compiler can tell, so their sums cannot be scheduled (and waited for) above the arithmetic `dep` depends on.  (Round-4
+// A/B against waiting for the records first: 11.76 against 12.71 ms per backward at NC = 804.)
 #define TTT_PIN_RECORDS(dep)                                                                                                              \
-    asm volatile("; records consumed from here"                                                                                           \
-                 : "+v"(pa[0][0]), "+v"(pa[0][1]), "+v"(pa[0][2]), "+v"(pa[0][3]), "+v"(pa[1][0]), "+v"(pa[1][1]), "+v"(pa[1][2]), "+v"(pa[1][3]), \
-                   "+v"(pa[2][0]), "+v"(pa[2][1]), "+v"(pa[2][2]), "+v"(pa[2][3]), "+v"(pa[3][0]), "+v"(pa[3][1]), "+v"(pa[3][2]), "+v"(pa[3][3]) \
-                 : "v"(dep))
-
-// OVL (round 4; the shipped instantiation has it on, the template parameter remains): the owners' partner-independent arithmetic runs
-// while the partner records are in flight; off = the round-3 order (wait for the records, then all the arithmetic).
-#define TTT_PIN_RECORDS16(dep)                                                                                                            \
     asm volatile("; records consumed from here"                                                                                           \
                  : "+v"(pb[0][0]), "+v"(pb[0][1]), "+v"(pb[1][0]), "+v"(pb[1][1]), "+v"(pb[2][0]), "+v"(pb[2][1]), "+v"(pb[3][0]), "+v"(pb[3][1]) \
                  : "v"(dep))
-// R16 (round 4; on in the shipped instantiation): the partial d(gZ2) tiles of the hand-over records travel as bf16 - half the
-// bytes a workgroup publishes (and drains in front of barrier Bb) and half the loads of the owners' chain; every workgroup
-// still sums the same four rounded partials in the same order, so dZ2 stays bit-identical on the four CUs.  Precision budget:
-// tools/diag/lr_gate_full_emul_cpu.py point "P_rec" - no gradient of the DiT fixtures moves beyond its run-to-run spread of
-// the other roundings (worst 3.0e-2 -> 3.6e-2 / 2.6e-2 -> 2.5e-2).  [t][PS16] bf16 inside the fp32 tile's area of the record.
+// The partial d(gZ2) tiles of the hand-over records travel as bf16 - half the bytes a workgroup publishes (and drains in front of
+// barrier Bb) and half the loads of the owners' chain; every workgroup still sums the same four rounded partials in the same order,
+// so dZ2 stays bit-identical on the four CUs.  Precision budget: tools/diag/lr_gate_full_emul_cpu.py point "P_rec" - no gradient of
+// the DiT fixtures moves beyond its run-to-run spread of the other roundings (worst 3.0e-2 -> 3.6e-2 / 2.6e-2 -> 2.5e-2).
+// [t][PS16] bf16 inside the record's tile area.  (Round-4 A/B against fp32 records: 11.82 against 14.16 ms per backward at NC = 804.)
 constexpr int PS16 = 72;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-// OWN16 (round 4; on in the shipped instantiation): the inner LayerNorm's owner rows of the step record (x_hat, y - target) are bf16
+// The inner LayerNorm's owner rows of the step record (x_hat, y - target) are bf16 too (round 4: 11.35 against 11.63 ms with fp32 rows).
 // Round 6: the dK / dQ tail is the group-sequential `mlp_bwd_tail5_kernel`, which rebuilds the per-step W1 and dW1' from one anchor per
 // checkpoint group - the derivers carry and store no W1, the compute waves store dW1 (fp32) at the top step of every group instead of a
 // packed image every step, gZ1 goes out in the T orientation.
-template <bool DBG, bool OVL, bool R16, int DW0, bool OWN16>
+template <bool DBG>
 __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
-    constexpr int OW0 = DW0 == 2 ? 4 : 2;                        // first owner wave (it polls the partner flags)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __bf16* Kt2 = reinterpret_cast<__bf16*>(smem + L_K);
     __bf16* Gt2 = reinterpret_cast<__bf16*>(smem + L_G);
@@ -219,7 +202,7 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
     // of every earlier step, so the rounding of that tile showed up 1 : 1 in the learning-rate-gate gradients (0.32 on the
     // 3-scene DiT fixture against 0.02 - 0.03 with this sum in fp32; tools/diag/lr_gate_full_emul_cpu.py has the ablation).
     // A step's 16 partials per feature (4 owner waves x 4 DPP rows of 4 tokens) go through the dW2 exchange region, which is
-    // idle between Ba and the publish_state behind Bc; owner wave 2 adds them while it waits for its partners.
+    // idle between Ba and the publish_state behind Bc; the first owner wave adds them while it waits for its partners.
     float* db2oL = reinterpret_cast<float*>(syncw + 4);            // [2][64] by iteration parity: the owners' share of db2 entering the step
 
     const int tid = threadIdx.x;
@@ -437,27 +420,17 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
                     P[ti] = mma(lfr(smem, L_R2, fr_idx(pp, pp, s), l), uN[ti][s], P[ti]);
                     P[ti] = mma(lfr(smem, L_R2, fr_idx(1 - pp, pp, s), l), ux, P[ti]);
                 }
-                if constexpr (R16) {
-                    const int vo = ((32 * ti + c) * PS16 + 32 * pp + 4 * h) * 2;   // [t][f] bf16 image (row stride PS16)
+                const int vo = ((32 * ti + c) * PS16 + 32 * pp + 4 * h) * 2;   // [t][f] bf16 image (row stride PS16)
 #pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const u32x4 v = __builtin_bit_cast(u32x4, pack(P[ti], s2));      // rows 8 s2 .. + 8: f = 16 s2 + 4 h + j | + 8
-                        const u32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-                        if (fast) {
-                            __builtin_amdgcn_raw_buffer_store_b64(lo, rX, vo + 32 * s2, xmine, 0);
-                            __builtin_amdgcn_raw_buffer_store_b64(hi, rX, vo + 32 * s2 + 16, xmine, 0);
-                        } else {
-                            __builtin_amdgcn_raw_buffer_store_b64(lo, rX, vo + 32 * s2, xmine, 16);
-                            __builtin_amdgcn_raw_buffer_store_b64(hi, rX, vo + 32 * s2 + 16, xmine, 16);
-                        }
-                    }
-                } else {
-                    const int vo = ((32 * ti + c) * PS + 32 * pp + 4 * h) * 4;   // [t][f] image (row stride PS), write-through
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const f32x4 v = {P[ti][4 * q4], P[ti][4 * q4 + 1], P[ti][4 * q4 + 2], P[ti][4 * q4 + 3]};
-                        if (fast) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rX, vo + 32 * q4, xmine, 0);
-                        else bst4f_sc1(rX, vo + 32 * q4, xmine, v);
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const u32x4 v = __builtin_bit_cast(u32x4, pack(P[ti], s2));      // rows 8 s2 .. + 8: f = 16 s2 + 4 h + j | + 8
+                    const u32x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
+                    if (fast) {
+                        __builtin_amdgcn_raw_buffer_store_b64(lo, rX, vo + 32 * s2, xmine, 0);
+                        __builtin_amdgcn_raw_buffer_store_b64(hi, rX, vo + 32 * s2 + 16, xmine, 0);
+                    } else {
+                        __builtin_amdgcn_raw_buffer_store_b64(lo, rX, vo + 32 * s2, xmine, 16);
+                        __builtin_amdgcn_raw_buffer_store_b64(hi, rX, vo + 32 * s2 + 16, xmine, 16);
                     }
                 }
             }
@@ -569,9 +542,9 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             if (cq == 0 && h == 0) ob2[fO + c] = db2v + db2oL[((i0 - p.chunk_lo) & 1) * 64 + fO + c] + poison;
         }
         if (p.last) __syncthreads();           // (the owners' final reduction)
-    } else if (wv != DW0 && wv != DW0 + 1) {
+    } else if (wv != FIRST_DERIVER && wv != FIRST_DERIVER + 1) {
         // =========================================================================================================== OWNERS
-        int ow = ((DW0 == 2 ? wv - 4 : (wv < DW0 ? wv - 2 : wv - 4)) << 6) | (tid & 63);      // 0 .. 255 over the four owner waves
+        int ow = ((wv - FIRST_OWNER) << 6) | (tid & 63);       // 0 .. 255 over the four owner waves
         int ot = ow >> 2, of0 = 16 * (ow & 3);                  // token, first of this thread's 16 features
         float dgam[16], dbet[16];
         if (p.first) {
@@ -644,8 +617,8 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             // column sums of the fp32 dZ2b: two DPP row shifts leave the sum of a row's four tokens in its lanes 12 .. 15
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                g[k] += dppq<0x114>(g[k]);                 // row_shr:4 (zero beyond the row)
-                g[k] += dppq<0x118>(g[k]);                 // row_shr:8
+                g[k] += dpp_f<0x114>(g[k]);                // row_shr:4 (zero beyond the row)
+                g[k] += dpp_f<0x118>(g[k]);                // row_shr:8
             }
             if ((tid & 12) == 12) {                        // partial (owner wave, row) x features of0 .. of0 + 16
                 float* pw = part + (ow >> 4) * 64 + of0;
@@ -656,7 +629,7 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
                 }
             }
         };
-        // owner wave 2, lane = feature: the owners' share of db2 entering the NEXT step = this one + the 16 partials (fixed order)
+        // first owner wave, lane = feature: the owners' share of db2 entering the NEXT step = this one + the 16 partials (fixed order)
         auto add_parts = [&](const float* part, const float* from, float* to) {
             float s4 = 0.f;
 #pragma unroll
@@ -670,7 +643,7 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             consume_step(0, L0, reinterpret_cast<float*>(exu));       // (exd is written by publish_state(i0) between P1 and P2)
         }
         owner_barrier();                       // P1
-        if (wv == OW0) add_parts(reinterpret_cast<const float*>(exu), nullptr, db2oL);
+        if (wv == FIRST_OWNER) add_parts(reinterpret_cast<const float*>(exu), nullptr, db2oL);
         owner_barrier();                       // P2
 
         unsigned long long t_prev = 0;
@@ -687,17 +660,12 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             // ---- requests of this iteration: the owner inputs of step i, the tiles / output-LayerNorm inputs of step j - all in
             //      flight across Ba ------------------------------------------------------------------------------------------------
             float xh[16], go[16];
-            u32x4 xg16[4];                     // own16: the two rows as bf16, 2 x 16 bytes each, converted behind Bb
+            u32x4 xg16[4];                     // the two owner rows as bf16, 2 x 16 bytes each, converted behind Bb
             const int so = sI + (int)SLOT4_FR;
-            if constexpr (OWN16) {
 #pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    xg16[u] = __builtin_amdgcn_raw_buffer_load_b128(rS, ow * 32 + 16 * u, so, 0);
-                    xg16[2 + u] = __builtin_amdgcn_raw_buffer_load_b128(rS, ow * 32 + 16 * u, so + (int)SLOT_OWN_ARR, 0);
-                }
-            } else {
-                ld16f(rS, ow * 64, so, xh);
-                ld16f(rS, ow * 64, so + (int)SLOT_OWN_ARR, go);
+            for (int u = 0; u < 2; ++u) {
+                xg16[u] = __builtin_amdgcn_raw_buffer_load_b128(rS, ow * 32 + 16 * u, so, 0);
+                xg16[2 + u] = __builtin_amdgcn_raw_buffer_load_b128(rS, ow * 32 + 16 * u, so + (int)SLOT_OWN_ARR, 0);
             }
             const float r = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rS, ot * 8, so + 3 * (int)SLOT_OWN_ARR, 0));
             StepLoads Lj;
@@ -726,18 +694,16 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             }
             // ---- O-C: hand-over ------------------------------------------------------------------------------------------------
             if (ow == 0) __hip_atomic_store(my_flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if constexpr (OWN16) {
 #pragma unroll
-                for (int u = 0; u < 2; ++u)
+            for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        xh[8 * u + 2 * w] = __builtin_bit_cast(float, xg16[u][w] << 16);
-                        xh[8 * u + 2 * w + 1] = __builtin_bit_cast(float, xg16[u][w] & 0xffff0000u);
-                        go[8 * u + 2 * w] = __builtin_bit_cast(float, xg16[2 + u][w] << 16);
-                        go[8 * u + 2 * w + 1] = __builtin_bit_cast(float, xg16[2 + u][w] & 0xffff0000u);
-                    }
-            }
-            if (wv == OW0) {
+                for (int w = 0; w < 4; ++w) {
+                    xh[8 * u + 2 * w] = __builtin_bit_cast(float, xg16[u][w] << 16);
+                    xh[8 * u + 2 * w + 1] = __builtin_bit_cast(float, xg16[u][w] & 0xffff0000u);
+                    go[8 * u + 2 * w] = __builtin_bit_cast(float, xg16[2 + u][w] << 16);
+                    go[8 * u + 2 * w + 1] = __builtin_bit_cast(float, xg16[2 + u][w] & 0xffff0000u);
+                }
+            if (wv == FIRST_OWNER) {
                 const int l = tid & 63;
                 if (more) add_parts(reinterpret_cast<const float*>(exd), db2oL + cur * 64, db2oL + (cur ^ 1) * 64);
                 if (l < 3) {
@@ -777,7 +743,7 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
                 }
                 if (l == 0) __hip_atomic_store(syncw, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             } else {
-                // (no bound of its own: wave 2 of this workgroup always arrives - its poll above is bounded by the wall clock -, and
+                // (no bound of its own: the first owner wave always arrives - its poll above is bounded by the wall clock -, and
                 // a bound counted in polls here could expire BEFORE that one and let these waves go on with stale records)
                 while (__hip_atomic_load(syncw, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < epoch) __builtin_amdgcn_s_sleep(1);
             }
@@ -786,22 +752,13 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             float dep[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             // all four records - this workgroup's own included - come back through memory with sc1 loads: no branch on cq,
             // and the same summation order q = 0..3 on all four workgroups -> bit-identical dZ2 everywhere
-            f32x4 pa[R16 ? 1 : 4][4];
-            u32x4 pb[4][2];                    // R16: 16 bf16 per record
+            u32x4 pb[4][2];                    // 16 bf16 per record
             {
-                if constexpr (R16) {
-                    const int vo = (ot * PS16 + of0) * 2;
+                const int vo = (ot * PS16 + of0) * 2;
 #pragma unroll
-                    for (int qq = 0; qq < 4; ++qq)
+                for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
-                        for (int u = 0; u < 2; ++u) pb[qq][u] = __builtin_amdgcn_raw_buffer_load_b128(rX, vo + 16 * u, xrec + qq * XCH_REC_BYTES, 16);
-                } else {
-                    const int vo = (ot * PS + of0) * 4;
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) pa[qq][u] = bld4f_sc1(rX, vo + 16 * u, xrec + qq * XCH_REC_BYTES);
-                }
+                    for (int u = 0; u < 2; ++u) pb[qq][u] = __builtin_amdgcn_raw_buffer_load_b128(rX, vo + 16 * u, xrec + qq * XCH_REC_BYTES, 16);
                 if (cq == 0 && (ow & 3) == 0) {            // workgroup 0 finishes d(eta): request the eight per-wave partials now
 #pragma unroll
                     for (int qq = 0; qq < 4; ++qq)
@@ -813,11 +770,9 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             }
             {
                 // ---- what needs no partner - gZ2 of this step in fp32 and its row statistics, the db2 term of d(eta) - runs while
-                // the records are in flight (round 4: the ISA used to wait for all sixteen loads first and start this arithmetic
-                // afterwards; the asm statement below pins the order)
+                // the records are in flight (round 4: the ISA used to wait for all the loads first and start this arithmetic
+                // afterwards; TTT_PIN_RECORDS below pins the order)
                 const float eta_t = etaL2[cur * 64 + ot];
-                if constexpr (!OVL && !R16) TTT_PIN_RECORDS(eta_t);
-                if constexpr (!OVL && R16) TTT_PIN_RECORDS16(eta_t);
                 float gxh[16], gz[16];
                 float s1g = 0.f, s2g = 0.f;
 #pragma unroll
@@ -836,28 +791,17 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
                     edb[k] = eta_t * db2;
                 }
                 se = sum4(se);
-                // the records are "produced" here as far as the compiler can tell: their sums cannot be scheduled (and waited
-                // for) above the arithmetic that `se` depends on
-                if constexpr (R16) {
-                    if constexpr (OVL) TTT_PIN_RECORDS16(se);
-                    // bf16 pair (lo, hi) of dword w = features 2w, 2w + 1: the same four partials in the same order on all four CUs
-                    auto lo = [](unsigned w) { return __builtin_bit_cast(float, w << 16); };
-                    auto hi = [](unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); };
+                TTT_PIN_RECORDS(se);
+                // bf16 pair (lo, hi) of dword w = features 2w, 2w + 1: the same four partials in the same order on all four CUs
+                auto lo = [](unsigned w) { return __builtin_bit_cast(float, w << 16); };
+                auto hi = [](unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); };
 #pragma unroll
-                    for (int u = 0; u < 2; ++u)
+                for (int u = 0; u < 2; ++u)
 #pragma unroll
-                        for (int w = 0; w < 4; ++w) {
-                            G_[8 * u + 2 * w] = ((lo(pb[0][u][w]) + lo(pb[1][u][w])) + lo(pb[2][u][w])) + lo(pb[3][u][w]);
-                            G_[8 * u + 2 * w + 1] = ((hi(pb[0][u][w]) + hi(pb[1][u][w])) + hi(pb[2][u][w])) + hi(pb[3][u][w]);
-                        }
-                } else {
-                    if constexpr (OVL) TTT_PIN_RECORDS(se);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const f32x4 v = ((pa[0][u] + pa[1][u]) + pa[2][u]) + pa[3][u];
-                        G_[4 * u] = v[0]; G_[4 * u + 1] = v[1]; G_[4 * u + 2] = v[2]; G_[4 * u + 3] = v[3];
+                    for (int w = 0; w < 4; ++w) {
+                        G_[8 * u + 2 * w] = ((lo(pb[0][u][w]) + lo(pb[1][u][w])) + lo(pb[2][u][w])) + lo(pb[3][u][w]);
+                        G_[8 * u + 2 * w + 1] = ((hi(pb[0][u][w]) + hi(pb[1][u][w])) + hi(pb[2][u][w])) + hi(pb[3][u][w]);
                     }
-                }
                 TTT_OSTAMP(1)                  // the four records have arrived
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
@@ -914,7 +858,7 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
             unsigned touch = 0u;
             if (p.prefetch && i - 2 >= p.chunk_lo) {
                 const int s2 = slot_off(i - 2) + (int)SLOT4_FR;
-                if (!(OWN16 && (ow & 64))) touch = __builtin_amdgcn_raw_buffer_load_b32(rS, ow * 128, s2, 0);      // (own16: the second halves of the first two arrays are unused)
+                if (!(ow & 64)) touch = __builtin_amdgcn_raw_buffer_load_b32(rS, ow * 128, s2, 0);      // (bf16 owner rows: the second halves of the first two arrays are unused)
                 if (ow < 452 - 256) touch += __builtin_amdgcn_raw_buffer_load_b32(rS, (256 + ow) * 128, s2, 0);
                 if (ow < 192) {
                     const __amdgpu_buffer_rsrc_t rT = ow < 64 ? rK : ow < 128 ? rQ : rO;
@@ -957,11 +901,11 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
         }
     } else {
         // =========================================================================================================== DERIVERS
-        const int pp = wv - DW0;                                // the 32 hidden units of compute wave pp
+        const int pp = wv - FIRST_DERIVER;                             // the 32 hidden units of compute wave pp
         const int l = tid & 63, h = l >> 5, c = l & 31;
         const int nO = 64 * cq + 32 * pp;
         DeriverBackend<DBG> bk{smem, (int)(threadIdx.x & 63)};
-        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * DW0) bk.dbg = reinterpret_cast<unsigned long long*>(p.dbg);
+        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * FIRST_DERIVER) bk.dbg = reinterpret_cast<unsigned long long*>(p.dbg);
         bwd4::AuxState st;
         // the state entering step `step` (a multiple of the checkpoint group size, or the end of the sequence): the forward's
         // checkpoint, or the state phase A wrote after the last step
@@ -997,12 +941,12 @@ __global__ __launch_bounds__(NTC) void mlp_bwd_cluster4_kernel(SweepParams4 p) {
         // DEBUG cycle stamps of deriver wave 0 of workgroup 0 (entries 28 .. 31: staging after Bd, derive_z1b, reverse_step, barriers)
         unsigned long long t_d = 0;
 #define TTT_DSTAMP(k)                                                                \
-        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * DW0) {              \
+        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * FIRST_DERIVER) {    \
             const unsigned long long _t = __builtin_readcyclecounter();              \
             p.dbg[28 + (k)] += _t - t_d;                                             \
             t_d = _t;                                                                \
         }
-        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * DW0) t_d = __builtin_readcyclecounter();
+        if (DBG && p.dbg != nullptr && blockIdx.x == 0 && tid == 64 * FIRST_DERIVER) t_d = __builtin_readcyclecounter();
         for (int i = i0; i >= p.chunk_lo; --i) {
             const bool more = i > p.chunk_lo;
             const int nxt = ((i0 - i) & 1) ^ 1;                 // tile buffer of step j = i - 1
@@ -1267,12 +1211,8 @@ unsigned read_sweep_fast_count() {      // DEBUG statistic: cluster workgroup la
     return v;
 }
 
-// (the owners' partner-independent arithmetic under the record loads - template parameter OVL; one box, NC = 804: with fp32 records
-// 14.15 ms per backward against 13.44 without, with bf16 records 11.76 against 12.71 - goes with the bf16 records)
-// Shipped instantiation (every parameter decided by an interleaved A/B on one MI355X, profiles/r4b - r4h; the losing
-// instantiations and their options were removed in round 5): bf16 hand-over records with the owners' partner-independent arithmetic
-// under the record loads (11.82 against 14.16 ms per backward at NC = 804), derivers on waves 2, 3 = SIMDs 2 / 3 beside two owner
-// waves (11.48 - 11.62 against 11.79 - 11.94), bf16 inner-LayerNorm owner rows (11.35 against 11.63).
+// (The sweep's form - bf16 hand-over records, owner arithmetic under the record loads, derivers on waves 2 / 3, bf16 owner rows - was
+// decided by interleaved A/Bs on one MI355X, profiles/r4b - r4h; the figures stand with each piece in b4 above.)
 
 namespace s4 {
 
@@ -1285,14 +1225,14 @@ void launch_sweep_cluster4(const SweepParams4& bp, int nbh, hipStream_t s) {
         std::lock_guard<std::mutex> lock(g_err_mutex);
         if (dev >= 0 && dev < 64 && !attr[dev]) {
             auto set = [&](auto kern) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, b4::LDS_CL); };
-            set(b4::mlp_bwd_cluster4_kernel<false, true, true, 2, true>);    set(b4::mlp_bwd_cluster4_kernel<true, true, true, 2, true>);
+            set(b4::mlp_bwd_cluster4_kernel<false>);    set(b4::mlp_bwd_cluster4_kernel<true>);
             (void)hipFuncSetAttribute((const void*)b4::mlp_bwd_tail5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, b4::LDS_TAIL5);
             attr[dev] = true;
         }
     }
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, blk, b4::LDS_CL, s, bp); };
-    if (bp.dbg != nullptr) go(b4::mlp_bwd_cluster4_kernel<true, true, true, 2, true>);        // (stage stamps: tools/op_bench.py --phases)
-    else go(b4::mlp_bwd_cluster4_kernel<false, true, true, 2, true>);
+    if (bp.dbg != nullptr) go(b4::mlp_bwd_cluster4_kernel<true>);      // (stage stamps: tools/op_bench.py --phases)
+    else go(b4::mlp_bwd_cluster4_kernel<false>);
 }
 
 void launch_tail5(const Tail5Args& a, int nbh, hipStream_t s) {

@@ -1,34 +1,17 @@
 // Device helpers shared by the TTT-MLP backward kernels (recompute ttt_mfma_rc4.hip, cluster sweep and tail ttt_mfma_bwd4.hip).
 #pragma once
 #include "ttt_mfma_dev.h"
+#include "ttt_dpp.h"
 
 namespace ttt {
 namespace mfma {
 using namespace ttt::mf;
 namespace b2 {
 
-
 constexpr int NT2 = 512;
 typedef __attribute__((address_space(3))) bf16x4 lds_b4;
 
 // ---- helpers shared with the revision-2 forward (same idioms) --------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum8(float v) {
-    v += dpp_f<0xB1>(v);
-    v += dpp_f<0x4E>(v);
-    v += dpp_f<0x141>(v);
-    return v;
-}
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int stride, int r0, int r1, int col0, int l) {
-    const int i = l & 15, g1 = (l >> 4) & 1;
-    const int off = (i >> 2) * stride + col0 + 16 * g1 + 4 * (i & 3);
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r0 * stride + off));
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r1 * stride + off));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 // operand fragment (outer = column in [col0, col0+32), contraction = rows of the 32-row block at row0, pi slot order s)
 __device__ __forceinline__ bf16x8 tr_pi(const __bf16* img, int row0, int s, int col0, int l) {
     const int h = l >> 5;
@@ -92,13 +75,6 @@ __device__ __forceinline__ void bld8f(__amdgpu_buffer_rsrc_t r, int voff, int so
     const f32x4 a = bld4f(r, voff, soff), b = bld4f(r, voff + 16, soff);
     o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
 }
-// write-through / L1-bypassing forms for the inter-workgroup exchange (aux 16 = sc1)
-__device__ __forceinline__ void bst4f_sc1(__amdgpu_buffer_rsrc_t r, int voff, int soff, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, 16);
-}
-__device__ __forceinline__ f32x4 bld4f_sc1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 16));
-}
 
 // carry area per (b,h), floats: natural-layout dW1 [64][256], dW2 [256][64], db1 [256], db2 [64], then per-thread dgamma / dbeta
 constexpr size_t C_DW1 = 0, C_DW2 = 64 * 256, C_DB1 = 2 * 64 * 256, C_DB2 = C_DB1 + 256, C_DG = C_DB2 + 64, C_DBT = C_DG + NT2 * 8,
@@ -124,7 +100,8 @@ struct SweepParams2 {
 
 
 // ---- cluster form: exchange records ------------------------------------------------------------------------------------
-// exchange record of one workgroup and step parity: the partial tile [64][PS] fp32 + the d(eta) partials of its two waves
+// exchange record of one workgroup and step parity: the partial tile's area (sized [64][PS] fp32; the sweep stores it as bf16,
+// ttt_mfma_bwd4.hip PS16) + the d(eta) partials of its two waves
 constexpr int XCH_PART_BYTES = 64 * PS * 4;
 constexpr int XCH_REC_BYTES = XCH_PART_BYTES + 2 * 64 * 4;
 constexpr size_t XCH_BH_BYTES = 2 * 4 * (size_t)XCH_REC_BYTES;

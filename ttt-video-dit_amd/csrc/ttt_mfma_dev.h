@@ -30,7 +30,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int TS = 72;            // LDS row stride of a [64][64] bf16 tile, in elements (144 B: 16-B aligned, conflict-free b128)
 constexpr int PS = 68;            // LDS row stride of a [64][64] fp32 partial tile, in floats (272 B)
 
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ f32x16 mma(bf16x8 a, bf16x8 b, f32x16 c) {
@@ -50,14 +49,6 @@ __device__ __forceinline__ bf16x8 pack(const f32x16& t, int s) {
     for (int e = 0; e < 8; ++e) r[e] = (__bf16)t[8 * s + e];
     return r;
 }
-// same, with a per-row scale: sc[r] multiplies register r (rows live in registers)
-__device__ __forceinline__ bf16x8 pack_scaled(const f32x16& t, const f32x16& sc, int s) {
-    bf16x8 r;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (__bf16)(t[8 * s + e] * sc[8 * s + e]);
-    return r;
-}
-
 // "pi read": operand fragment for k-slice (s) of a 32-wide column block starting at col0, from a
 // row-major bf16 LDS tile; `rowp` points at this lane's row.  Two 8-byte reads.
 __device__ __forceinline__ bf16x8 pi_read(const __bf16* rowp, int col0, int s, int h) {
@@ -67,6 +58,24 @@ __device__ __forceinline__ bf16x8 pi_read(const __bf16* rowp, int col0, int s, i
 #pragma unroll
     for (int e = 0; e < 4; ++e) { r[e] = lo[e]; r[4 + e] = hi[e]; }
     return r;
+}
+
+// transposed LDS read (ds_read_b64_tr_b16): operand fragment (outer = column, contract = row) of a row-major bf16 image;
+// rows r0..r0+3 and r1..r1+3 fill the 8 k-slots, 32 outer columns start at col0; `img` row stride = stride elems.
+__device__ __forceinline__ bf16x8 tr_frag(const __bf16* img, int stride, int r0, int r1, int col0, int l) {
+    const int i = l & 15, g1 = (l >> 4) & 1;
+    const int off = (i >> 2) * stride + col0 + 16 * g1 + 4 * (i & 3);
+    // NB: no per-element __builtin_bit_cast on vector elements (it reads element 0 for every index): use the
+    // bf16-typed builtin and concatenate whole vectors.
+    typedef __attribute__((address_space(3))) bf16x4 lds_b4;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r0 * stride + off));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(img + r1 * stride + off));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+// same, in the pi k-slot order of an in-place C tile fragment s of the 32-row block starting at row0
+__device__ __forceinline__ bf16x8 tr_frag_pi(const __bf16* img, int stride, int row0, int s, int col0, int l) {
+    const int h = l >> 5;
+    return tr_frag(img, stride, row0 + 16 * s + 4 * h, row0 + 16 * s + 8 + 4 * h, col0, l);
 }
 
 // identity fragment (as B operand) for the pi slot order: I[slot(h,e)][j=c] = (pi_s(h,e) == c)
@@ -97,7 +106,6 @@ __device__ __forceinline__ float sig2u(float x, float x2) {
     const float e = __builtin_amdgcn_exp2f(x * __builtin_fmaf(x2, GELU_K1, GELU_K0));
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
-__device__ __forceinline__ float sigmoid2u(float x, float x2) { return sig2u(x, x2); }
 __device__ __forceinline__ void gelu_fwd_grad(float x, float& y, float& dy) {
     const float x2 = x * x;
     const float s = sig2u(x, x2);                // (1 + tanh u) / 2
@@ -106,15 +114,10 @@ __device__ __forceinline__ void gelu_fwd_grad(float x, float& y, float& dy) {
 }
 __device__ __forceinline__ float gelu_fwd(float x) { return x * sig2u(x, x * x); }
 
-__device__ __forceinline__ float gelu_grad_only(float x) {
-    float y, dy;
-    gelu_fwd_grad(x, y, dy);
-    return dy;
-}
 // y = gelu, dy = gelu', d2y = gelu''   (gelu'' = q u' + x q (u''/2 - t u'^2), q = 1 - t^2)
 __device__ __forceinline__ void gelu_fwd_grad2(float x, float& y, float& dy, float& d2y) {
     const float x2 = x * x;
-    const float s = sigmoid2u(x, x2);
+    const float s = sig2u(x, x2);
     const float t = 2.0f * s - 1.0f;
     const float q = 4.0f * s * (1.0f - s);
     const float du = GELU_A + GELU_3AC * x2;
@@ -158,56 +161,8 @@ __device__ __forceinline__ void gelu_fwd_tile_pk(f32x16& z) {
 
 // ------------------------------------------------------------------------------------------------
 // LDS geometry shared by the scan kernels
-constexpr int NT = 256;
 constexpr int TILE_ELEMS = 64 * TS;                          // one padded [64][64] bf16 tile
 
-// write one wave's partial [f][t] tiles (rows=f, lane=t) to red[w][t][f]
-__device__ __forceinline__ void write_partial(float* redw, const f32x16 (&P)[2][2], int h, int c) {
-#pragma unroll
-    for (int fj = 0; fj < 2; ++fj)
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v = {P[fj][ti][4 * q], P[fj][ti][4 * q + 1], P[fj][ti][4 * q + 2], P[fj][ti][4 * q + 3]};
-                *reinterpret_cast<f32x4*>(redw + (32 * ti + c) * PS + 32 * fj + 8 * q + 4 * h) = v;
-            }
-}
-
-// owner lane (token t, 16 features f0..f0+15): z = sum of the four partials (+ bias[f] if given)
-__device__ __forceinline__ void gather_partial(const float* red, const float* bias, int t, int f0, float (&z)[16]) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) z[j] = bias ? bias[f0 + j] : 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(red + ((size_t)w * 64 + t) * PS + f0 + 4 * q);
-            z[4 * q] += v[0]; z[4 * q + 1] += v[1]; z[4 * q + 2] += v[2]; z[4 * q + 3] += v[3];
-        }
-}
-
-// sum over the 4 lanes (l, l^16, l^32, l^48) that share an owner token
-__device__ __forceinline__ float quad_add(float v) { return xor_add(xor_add(v, 16), 32); }
-
-// LayerNorm statistics of a 64-wide row spread over 4 lanes, 16 values each
-__device__ __forceinline__ void row_stats(const float (&z)[16], float eps, float& mu, float& rstd) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) s += z[j];
-    mu = quad_add(s) * (1.0f / 64.0f);
-    float v = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { const float d = z[j] - mu; v += d * d; }
-    rstd = 1.0f / sqrtf(quad_add(v) * (1.0f / 64.0f) + eps);
-}
-
-__device__ __forceinline__ void load16_bf16(const __bf16* p, float (&o)[16]) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-    const bf16x8 b = *reinterpret_cast<const bf16x8*>(p + 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { o[j] = (float)a[j]; o[8 + j] = (float)b[j]; }
-}
 __device__ __forceinline__ void store16_bf16(__bf16* p, const float (&v)[16]) {
     bf16x8 a, b;
 #pragma unroll
@@ -253,25 +208,6 @@ constexpr size_t SLOT_OWN = 3 * SLOT_OWN_ARR + 64 * 8;
 constexpr size_t SLOT_G = 64 * 64 * 2;                                   // gZ2 tile, bf16 row-major
 
 __device__ __forceinline__ int fr_idx(int a, int b, int s) { return (a * 2 + b) * 2 + s; }
-// owner rows: `own` = the record's owner area; token ot, features of0 .. of0 + N - 1
-template <int N>
-__device__ __forceinline__ void st_own(char* own, int arr, int ot, int of0, const float (&v)[N]) {
-    float* p = reinterpret_cast<float*>(own + (size_t)arr * SLOT_OWN_ARR) + ot * 64 + of0;
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-        f32x4 x = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-        *reinterpret_cast<f32x4*>(p + 4 * q) = x;
-    }
-}
-template <int N>
-__device__ __forceinline__ void ld_own(const char* own, int arr, int ot, int of0, float (&v)[N]) {
-    const float* p = reinterpret_cast<const float*>(own + (size_t)arr * SLOT_OWN_ARR) + ot * 64 + of0;
-#pragma unroll
-    for (int q = 0; q < N / 4; ++q) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(p + 4 * q);
-        v[4 * q] = x[0]; v[4 * q + 1] = x[1]; v[4 * q + 2] = x[2]; v[4 * q + 3] = x[3];
-    }
-}
 __device__ __forceinline__ float* own_stats(char* own, int ot) {
     return reinterpret_cast<float*>(own + 3 * SLOT_OWN_ARR) + 2 * ot;
 }

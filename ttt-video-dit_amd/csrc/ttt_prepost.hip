@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "../../include/ttt_hip.h"
 #include "ttt_prepost.h"
+#include "ttt_dpp.h"
 
 namespace ttt {
 namespace prepost {
@@ -21,16 +22,6 @@ namespace prepost {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float sum8(float v) {   // sum over the 8 lanes of an aligned group
-    v += dpp_f<0xB1>(v);
-    v += dpp_f<0x4E>(v);
-    v += dpp_f<0x141>(v);
-    return v;
-}
 __device__ __forceinline__ void ld8(const __bf16* p, float (&o)[8]) {
     const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
 #pragma unroll

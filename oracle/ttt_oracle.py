@@ -472,3 +472,78 @@ def make_inputs(kind: str, B, NH, NC, CS, Fd, seed=0, dtype=torch.float32, base_
     else:
         d.update(W1=0.02 * rn(NH, Fd, Fd), b1=0.01 * rn(NH, 1, Fd))
     return {k: v.to(dtype) for k, v in d.items()}
+
+
+# --------------------------------------------------------------------------- rounding model of the MFMA forward scans
+# One primal step in fp64 with a bf16 rounding at every point where the MFMA kernels round (the step description at the top of
+# csrc/ttt_mfma2.hip; csrc/ttt_mlp16_body.h / ttt_lin16_body.h): the "reference alone" level of the one-step metrics of
+# tests/scan_cases.py - what a kernel that rounds where these do, and is otherwise exact, is away from the fp64 step.  The points:
+#   "W"      the packed bf16 operand copies of W1 / W2 in every product that reads the state (the fp32 accumulators that carry the
+#            state stay unrounded: the updates add to them)
+#   "X2"     the X2 = gelu(Z1) image: operand of Z2 and of the W2 update
+#   "Gs"     Gs = -eta gZ2 (TTT-Linear: -eta gZ1), the operand of every update and of gX2; b2 (TTT-Linear: b1) sums it
+#   "gZ1s"   gZ1s = (Gs W2^T) gelu'(Z1), the operand of the W1 update
+#   "b1_sum" b1 sums the ROUNDED gZ1s (mini-batch 16: a ones-MFMA over the packed tile; the mini-batch-64 kernel sums fp32 values)
+#   "X2b"    X2b = gelu(Z1b), operand of Z2b
+#   "out"    the bf16 output store
+MLP_ROUND_POINTS = ("W", "X2", "Gs", "gZ1s", "b1_sum", "X2b", "out")
+MLP_ROUND_CS64 = frozenset(MLP_ROUND_POINTS) - {"b1_sum"}
+MLP_ROUND_CS16 = frozenset(MLP_ROUND_POINTS)
+LIN_ROUND_POINTS = ("W", "Gs", "out")
+LIN_ROUND = frozenset(LIN_ROUND_POINTS)
+
+
+def _bf(x):
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def _mlp_step_scaled(W1, b1, W2, b2, Q, K, V, eta, gam, bet, eps, on):
+    """the primal step with eta carried inside Gs, as the kernels carry it (the row scaling commutes with the products)"""
+    r = lambda name, x: _bf(x) if name in on else x
+    Fd = Q.shape[-1]
+    T = lambda x: x.transpose(-1, -2)
+    W1o, W2o = r("W", W1), r("W", W2)
+    Z1 = K @ W1o + b1
+    X2 = r("X2", gelu_tanh(Z1))
+    D1 = gelu_bwd(Z1)
+    Z2 = X2 @ W2o + b2
+    xh, std = _ln_stats(Z2, eps)
+    gxh = (gam * xh + bet - (V - K)) * gam
+    gZ2 = (Fd * gxh - gxh.sum(-1, keepdim=True) - xh * (gxh * xh).sum(-1, keepdim=True)) / (Fd * std)
+    Gs = r("Gs", -eta * gZ2)
+    gZ1s = (Gs @ T(W2o)) * D1
+    gZ1o = r("gZ1s", gZ1s)
+    W1n = W1 + T(K) @ gZ1o
+    b1n = b1 + (gZ1o if "b1_sum" in on else gZ1s).sum(-2, keepdim=True)
+    W2n = W2 + T(X2) @ Gs
+    b2n = b2 + Gs.sum(-2, keepdim=True)
+    X2b = r("X2b", gelu_tanh(Q @ r("W", W1n) + b1n))
+    xhl, _ = _ln_stats(X2b @ r("W", W2n) + b2n, eps)
+    return (W1n, b1n, W2n, b2n), r("out", Q + gam * xhl + bet)
+
+
+def mlp_step_rounded(W1, b1, W2, b2, Q, K, V, eta, gam, bet, eps=LN_EPS, on=MLP_ROUND_CS64):
+    """``_mlp_step_primal`` with the roundings named in ``on`` -> (state, out).  With no point switched on it IS the primal step."""
+    if not on:
+        return _mlp_step_primal(W1, b1, W2, b2, Q, K, V, eta, gam, bet, eps)[:2]
+    return _mlp_step_scaled(W1, b1, W2, b2, Q, K, V, eta, gam, bet, eps, frozenset(on))
+
+
+def _lin_step_scaled(W1, b1, Q, K, V, eta, gam, bet, eps, on):
+    r = lambda name, x: _bf(x) if name in on else x
+    Fd = Q.shape[-1]
+    xh, std = _ln_stats(K @ r("W", W1) + b1, eps)
+    gxh = (gam * xh + bet - (V - K)) * gam
+    gZ1 = (Fd * gxh - gxh.sum(-1, keepdim=True) - xh * (gxh * xh).sum(-1, keepdim=True)) / (Fd * std)
+    Gs = r("Gs", -eta * gZ1)
+    W1n = W1 + K.transpose(-1, -2) @ Gs
+    b1n = b1 + Gs.sum(-2, keepdim=True)
+    xhl, _ = _ln_stats(Q @ r("W", W1n) + b1n, eps)
+    return (W1n, b1n), r("out", Q + gam * xhl + bet)
+
+
+def lin_step_rounded(W1, b1, Q, K, V, eta, gam, bet, eps=LN_EPS, on=LIN_ROUND):
+    """``_lin_step_primal`` with the roundings named in ``on`` -> (state, out).  With no point switched on it IS the primal step."""
+    if not on:
+        return _lin_step_primal(W1, b1, Q, K, V, eta, gam, bet, eps)[:2]
+    return _lin_step_scaled(W1, b1, Q, K, V, eta, gam, bet, eps, frozenset(on))

@@ -90,6 +90,36 @@ ATTN_TOL = {
 # regime sets these (the other metrics as ATTN_TOL).
 ATTN_TOL_LARGE = dict(ATTN_TOL, ulp_frac=5e-3, row=5e-2, lse=5e-4)
 
+# Tolerances of ONE STEP of the forward TTT scans against oracle/ttt_oracle.py, stepped from the scan's own checkpoints
+# (tests/scan_cases.py: the metrics; tests/test_scan_oracle_gpu.py), fixed by the sensitivity table of
+# tests/test_scan_oracle_cpu.py: each >= 2x the larger of the oracle's rounding model (mlp_step_rounded / lin_step_rounded, worst
+# over the cases of the GPU file) and the kernels' worst value measured on an MI355X (SCAN_MEASURED), each <= 1/3 of the nearest
+# mutation its metric must catch.
+#   metric       rounding model   MI355X    threshold   nearest must-catch mutation (its distance)
+#   delta        3.6e-3           3.5e-3    1e-2        LayerNorm epsilon 1e-6, TTT-MLP only (3.7e-2); unbiased inner variance (5.0e-2)
+#   delta_block  6.2e-3           6.2e-3    1.5e-2      update x 1.05 in one 32-wide block (5.0e-2)
+#   row          5.5e-3           5.1e-3    2e-2        Q of step i + 1 in the output path (2.1e-1)
+#   ulp_frac     0.094            0.093     0.25        none of its own (unbiased output variance: 0.75)
+#   ulp_max      13.3             13.3      32          none of its own
+#   gain         7.9e-4           5.5e-4    2.5e-3      unbiased output variance (7.9e-3)
+# Not separated by any metric, reported by the table: erf GELU in place of tanh GELU (delta 5e-7: |Z1| << 1 on these inputs) and,
+# for TTT-Linear, epsilon 1e-6 (delta 4e-3 .. 6e-3).
+SCAN_TOL = {
+    "delta": 1e-2,          # worst rel-L2 of one (b, h, step) state delta, each of W1, b1, W2, b2
+    "delta_block": 1.5e-2,  # the same of one 32-wide block of the hidden units / the features: the slice of one wave
+    "row": 2e-2,            # worst rel-L2 of one (b, h, step, token) output row against the bf16-rounded oracle
+    "ulp_frac": 0.25,       # fraction of outputs more than 1 bf16 ulp from the fp64 step (floor: 1/8 of the RMS)
+    "ulp_max": 32.0,        # largest distance in ulps
+    "gain": 2.5e-3,         # worst |least-squares gain - 1| of the output's LayerNorm part of one (b, h, step)
+}
+# The generic kernels: fp32 arithmetic, only the output store rounds (to bf16; nothing with fp32 activations).  The table's second
+# column; its reference-alone level is the oracle's step in fp32 (delta 1.7e-5: the fp32 spacing of the state against its delta;
+# row 1.0e-3, gain 2.5e-4: the bf16 store), the MI355X values are SCAN_MEASURED_GENERIC (row 1.1e-3, gain 3.4e-4).
+SCAN_TOL_GENERIC = dict(SCAN_TOL, delta=1e-4, delta_block=1e-4, row=5e-3, ulp_frac=1e-2, ulp_max=2.0, gain=1e-3)
+# the kernels' worst values on an MI355X over the cases of test_scan_oracle_gpu.py (profiles/r9_scan_oracle_gpu.log)
+SCAN_MEASURED = {"delta": 0.00353, "delta_block": 0.00616, "row": 0.00508, "ulp_frac": 0.0928, "ulp_max": 13.3, "gain": 0.000548}
+SCAN_MEASURED_GENERIC = {"delta": 1.36e-05, "delta_block": 1.45e-05, "row": 0.00111, "ulp_frac": 0.0, "ulp_max": 0.5, "gain": 0.000339}
+
 
 def scene_meta(text_length, num_chunks, num_frames, H, W):
     """SequenceMetadata of ``num_chunks`` scenes of ``text_length`` text tokens over ``num_frames`` H x W latent frames"""

@@ -37,16 +37,21 @@
 extern "C" {
 #endif
 
-/* 2 (round 4): ttt_hip_mlp_forward / _backward return -3 (sticky: an earlier backward hand-over timed out; acknowledge with
- * ttt_hip_sweep_error_clear), -10 (fewer than 4 compute units visible), -11 (no host-mapped error word), -12 (a HIP event /
- * stream call of the backward's two-stream schedule failed); the round-1 exports ttt_hip_debug_variant / ttt_hip_debug_helpers
- * are gone.  1: rounds 1 - 3. */
-/* 5 (round 6): ttt_hip_mlp_forward_workspace is non-zero for the MFMA scan at mini-batches of 64 - the forward runs as a PAIR of
- * workgroups per (b,h) (the state chain on one CU publishes the updated state per step into a ring of records in the workspace, a second
- * CU runs the output path from them: same bits, -25 % per scan) - and ttt_hip_mlp_forward_chunk USES its workspace arguments (NULL / too
- * small: the one-workgroup scan, as ABI 4 callers get it).  A pair whose second workgroup is never scheduled gives up after 2 s, poisons
- * its outputs with NaN and sets the sticky error that ttt_hip_sweep_error_clear() acknowledges (return code -3 of the next call), like
- * the backward's cluster.  Signatures unchanged.  4: ttt_hip_stream_create_masked / _destroy / ttt_hip_debug_placement_probe. */
+/* ABI version history (a binding compares ttt_hip_abi_version() with the version it was written against):
+ * 1: rounds 1 - 3.
+ * 2 (round 4): ttt_hip_mlp_forward / _backward return -3 (sticky: an earlier backward hand-over timed out; acknowledge with
+ *    ttt_hip_sweep_error_clear), -10 (fewer than 4 compute units visible), -11 (no host-mapped error word), -12 (a HIP event /
+ *    stream call of the backward's two-stream schedule failed); the round-1 exports ttt_hip_debug_variant / ttt_hip_debug_helpers
+ *    are gone.
+ * 3 (round 5): ttt_hip_pre_backward_ld / ttt_hip_attn_pre_backward_ld, ttt_hip_mlp_forward_chunk, ttt_hip_pre_forward_range /
+ *    ttt_hip_post_forward_range added.
+ * 4 (round 6): ttt_hip_stream_create_masked / _destroy / ttt_hip_debug_placement_probe added, the tensor entry points unchanged.
+ * 5 (round 6): ttt_hip_mlp_forward_workspace is non-zero for the MFMA scan at mini-batches of 64 - the forward runs as a PAIR of
+ *    workgroups per (b,h) (the state chain on one CU publishes the updated state per step into a ring of records in the workspace, a
+ *    second CU runs the output path from them: same bits, -25 % per scan) - and ttt_hip_mlp_forward_chunk USES its workspace arguments
+ *    (NULL / too small: the one-workgroup scan, as ABI 4 callers get it).  A pair whose second workgroup is never scheduled gives up
+ *    after 2 s, poisons its outputs with NaN and sets the sticky error that ttt_hip_sweep_error_clear() acknowledges (return code -3
+ *    of the next call), like the backward's cluster.  Signatures unchanged. */
 #define TTT_HIP_ABI_VERSION 5
 
 enum { TTT_DTYPE_BF16 = 0, TTT_DTYPE_F32 = 1 };
@@ -286,14 +291,23 @@ void        ttt_hip_debug_timing(void* device_buffer);
 /* DEBUG: force the number of checkpoint groups the MFMA backward re-materialises per chunk (0 = automatic,
  * sized to cover the 256 CUs); lets tests exercise the chunk-to-chunk gradient hand-over at small sizes. */
 void        ttt_hip_debug_groups_per_chunk(int groups);
-/* DEBUG knobs by name (five; every A/B option of rounds 2 - 4 was decided on hardware and removed with the losing code in round 5):
- * "groups_per_chunk" (checkpoint groups per backward chunk, 0 = automatic: tests exercise the chunk hand-over at small sizes),
- * "overlap_tail" (TTT-MLP backward: 1 (default) = the tail kernel of a chunk runs on an internal side stream beside the next chunk's
- * sweep and the caller's stream joins it before the call returns; 0 = everything on the caller's stream; identical results),
- * "fast_records" (sweep hand-over: 1 (default) = plain, L2-resident records once the four workgroups of a cluster have proven that they
- * share an XCD; 0 = write-through records always; identical results), "sweep_fast_count" (query: returns -2 - the number of cluster
- * workgroup launches that took the plain form), "sweep_fault" (fault injection for the tests of the hand-over failure path: workgroup
- * 3 of every backward cluster leaves before its first hand-over).  Returns 0, or -1 for an unknown name. */
+/* DEBUG knobs by name (every A/B option of rounds 2 - 4 was decided on hardware and removed with the losing code in round 5).
+ * Identical results whatever the setting, except for the two fault injections:
+ *   "groups_per_chunk"  checkpoint groups per backward chunk, 0 = automatic: tests exercise the chunk hand-over at small sizes
+ *                       (the same setter as ttt_hip_debug_groups_per_chunk);
+ *   "overlap_tail"      TTT-MLP backward schedule: 2 (default) = the tail kernel of chunk c and the recompute of chunk c-2 run on
+ *                       internal side streams beside the sweep of chunk c-1, joined into the caller's stream before the call returns;
+ *                       1 = the tail only; 0 = everything on the caller's stream;
+ *   "fast_records"      sweep hand-over: 1 (default) = plain, L2-resident records once the four workgroups of a cluster have proven
+ *                       that they share an XCD; 0 = write-through records always;
+ *   "sweep_fast_count"  query: returns -2 - the number of cluster workgroup launches that took the plain form;
+ *   "deriver_split"     sweep: 1 (default) = barrier Bc inside the derivers' reverse step; 0 = behind it;
+ *   "attn_prio"         attention backward: 1 (default) = a wave-priority raise around one MFMA cluster per kernel; 0 = without;
+ *   "scan_pair"         forward scan at mini-batches of 64: 1 (default) = a pair of workgroups per (b,h); 0 = one;
+ *   "sweep_fault"       fault injection for the tests of the hand-over failure path: workgroup 3 of every backward cluster leaves
+ *                       before its first hand-over;
+ *   "scan_fault"        fault injection: the output-path workgroup of every forward scan pair leaves at once.
+ * Returns 0, or -1 for an unknown name. */
 int         ttt_hip_debug_option(const char* name, int value);
 /* DEBUG: device buffer (>= 120000 floats) receiving the step-0 intermediates of workgroup 0 (NULL = off). */
 /* TTT-MLP backward, cluster form (four workgroups per (b,h) exchanging partial tiles inside the launch; at most n_cu / 4

@@ -46,6 +46,19 @@ static int post_launch(const char* what) {
 
 #define NEED(p) do { if (!(a->p)) return fail("ttt_hip: null pointer argument %s", #p); } while (0)
 
+// the 15 tensors of the TTT-MLP forward: ttt_hip_mlp_forward and ttt_hip_mlp_forward_chunk
+static int check_mlp_fwd_args(const ttt_mlp_fwd_args* a) {
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(W1_init); NEED(b1_init); NEED(W2_init); NEED(b2_init);
+    NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints); NEED(XQW);
+    return 0;
+}
+
+// a strided ttt_attn_tensor `t` into the flat fields of an attention parameter block: pointer p.PTR, strides p.PRE_sb / _sh / _ss
+#define ATTN_TENSOR(p, PTR, PRE, t) \
+    do { p.PTR = (decltype(p.PTR))(t).ptr; p.PRE##_sb = (t).stride_b; p.PRE##_sh = (t).stride_h; p.PRE##_ss = (t).stride_s; } while (0)
+
 extern "C" {
 
 int ttt_hip_abi_version(void) { return TTT_HIP_ABI_VERSION; }
@@ -145,11 +158,7 @@ size_t ttt_hip_linear_forward_workspace(const ttt_dims* d) { return ws_bytes(d, 
 size_t ttt_hip_linear_backward_workspace(const ttt_dims* d) { return ws_bytes(d, false, true); }
 
 int ttt_hip_mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
-    NEED(W1_init); NEED(b1_init); NEED(W2_init); NEED(b2_init);
-    NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints); NEED(XQW);
+    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
     int r = resolve(d, true, false);
     if (r < 0) return fail("ttt_hip: mlp_forward: unsupported geometry/dtype for the requested impl");
     if (wsb < ws_bytes(d, true, false) || (ws_bytes(d, true, false) && !ws)) return fail("ttt_hip: mlp_forward: workspace too small");
@@ -161,11 +170,7 @@ int ttt_hip_mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, 
 
 int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                               float* W2_final, float* b2_final, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
-    NEED(W1_init); NEED(b1_init); NEED(W2_init); NEED(b2_init);
-    NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints); NEED(XQW);
+    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
     if (resolve(d, true, false) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
         return fail("ttt_hip: mlp_forward_chunk: only the MFMA scan (mini-batches of 64 or 16) continues from a state");
     if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
@@ -337,12 +342,8 @@ int ttt_hip_attn_forward(const ttt_attn_fwd_args* a, void* stream) {
     if (a->B <= 0 || a->NH <= 0 || a->S <= 0) return fail("ttt_hip: attention: non-positive dimension");
     if (check_attn_tensor(a->Q, "Q") || check_attn_tensor(a->K, "K") || check_attn_tensor(a->V, "V") || check_attn_tensor(a->O, "O")) return -1;
     ttt::attn::FwdParams p = {};
-    p.Q = (const __bf16*)a->Q.ptr; p.K = (const __bf16*)a->K.ptr; p.V = (const __bf16*)a->V.ptr; p.O = (__bf16*)a->O.ptr;
+    ATTN_TENSOR(p, Q, q, a->Q); ATTN_TENSOR(p, K, k, a->K); ATTN_TENSOR(p, V, v, a->V); ATTN_TENSOR(p, O, o, a->O);
     p.LSE = a->LSE;
-    p.q_sb = a->Q.stride_b; p.q_sh = a->Q.stride_h; p.q_ss = a->Q.stride_s;
-    p.k_sb = a->K.stride_b; p.k_sh = a->K.stride_h; p.k_ss = a->K.stride_s;
-    p.v_sb = a->V.stride_b; p.v_sh = a->V.stride_h; p.v_ss = a->V.stride_s;
-    p.o_sb = a->O.stride_b; p.o_sh = a->O.stride_h; p.o_ss = a->O.stride_s;
     p.B = a->B; p.NH = a->NH; p.S = a->S; p.scale = a->scale;
     ttt::attn::launch_forward(p, (hipStream_t)stream);
     return post_launch("attn_forward");
@@ -356,17 +357,9 @@ int ttt_hip_attn_backward(const ttt_attn_bwd_args* a, void* stream) {
     if (check_attn_tensor(a->Q, "Q") || check_attn_tensor(a->K, "K") || check_attn_tensor(a->V, "V") || check_attn_tensor(a->O, "O") ||
         check_attn_tensor(a->dO, "dO") || check_attn_tensor(a->dQ, "dQ") || check_attn_tensor(a->dK, "dK") || check_attn_tensor(a->dV, "dV")) return -1;
     ttt::attn::BwdParams p = {};
-    p.Q = (const __bf16*)a->Q.ptr; p.K = (const __bf16*)a->K.ptr; p.V = (const __bf16*)a->V.ptr; p.O = (const __bf16*)a->O.ptr;
-    p.dO = (const __bf16*)a->dO.ptr; p.dQ = (__bf16*)a->dQ.ptr; p.dK = (__bf16*)a->dK.ptr; p.dV = (__bf16*)a->dV.ptr;
+    ATTN_TENSOR(p, Q, q, a->Q); ATTN_TENSOR(p, K, k, a->K); ATTN_TENSOR(p, V, v, a->V); ATTN_TENSOR(p, O, o, a->O);
+    ATTN_TENSOR(p, dO, do, a->dO); ATTN_TENSOR(p, dQ, dq, a->dQ); ATTN_TENSOR(p, dK, dk, a->dK); ATTN_TENSOR(p, dV, dv, a->dV);
     p.LSE = a->LSE; p.Delta = a->Delta;
-    p.q_sb = a->Q.stride_b; p.q_sh = a->Q.stride_h; p.q_ss = a->Q.stride_s;
-    p.k_sb = a->K.stride_b; p.k_sh = a->K.stride_h; p.k_ss = a->K.stride_s;
-    p.v_sb = a->V.stride_b; p.v_sh = a->V.stride_h; p.v_ss = a->V.stride_s;
-    p.o_sb = a->O.stride_b; p.o_sh = a->O.stride_h; p.o_ss = a->O.stride_s;
-    p.do_sb = a->dO.stride_b; p.do_sh = a->dO.stride_h; p.do_ss = a->dO.stride_s;
-    p.dq_sb = a->dQ.stride_b; p.dq_sh = a->dQ.stride_h; p.dq_ss = a->dQ.stride_s;
-    p.dk_sb = a->dK.stride_b; p.dk_sh = a->dK.stride_h; p.dk_ss = a->dK.stride_s;
-    p.dv_sb = a->dV.stride_b; p.dv_sh = a->dV.stride_h; p.dv_ss = a->dV.stride_s;
     p.B = a->B; p.NH = a->NH; p.S = a->S; p.scale = a->scale;
     ttt::attn::launch_backward(p, (hipStream_t)stream);
     return post_launch("attn_backward");
@@ -405,9 +398,8 @@ int ttt_hip_attn_pre_backward_ld(int B, int S, int NH, int n_text, float eps, co
     if (n_text < S && (!cos_table || !sin_table)) return fail("ttt_hip: attn_pre_backward: null rope table");
     if (check_attn_tensor(*dq, "dq") || check_attn_tensor(*dk, "dk")) return -1;
     ttt::attn::PreBwdParams p = {};
-    p.q_raw = (const __bf16*)q_raw; p.k_raw = (const __bf16*)k_raw; p.dq = (const __bf16*)dq->ptr; p.dk = (const __bf16*)dk->ptr;
-    p.dq_sb = dq->stride_b; p.dq_sh = dq->stride_h; p.dq_ss = dq->stride_s;
-    p.dk_sb = dk->stride_b; p.dk_sh = dk->stride_h; p.dk_ss = dk->stride_s;
+    p.q_raw = (const __bf16*)q_raw; p.k_raw = (const __bf16*)k_raw;
+    ATTN_TENSOR(p, dq, dq, *dq); ATTN_TENSOR(p, dk, dk, *dk);
     p.wq = wq; p.wk = wk; p.cos = cos_table; p.sin = sin_table;
     p.dq_raw = (__bf16*)dq_raw; p.dk_raw = (__bf16*)dk_raw; p.part = part; p.ld_out = (long)ld_out;
     p.B = B; p.S = S; p.NH = NH; p.n_text = n_text; p.eps = eps;

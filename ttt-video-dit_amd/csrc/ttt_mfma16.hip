@@ -185,13 +185,7 @@ void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*
     // a part of the sequence (mlp_forward_chunk): p.NC steps from step p.ck0 of p.NCs, the pointers those of the whole sequence
     // (at CS = 16 a part may start at any step, so ck0 carries the first STEP, not a checkpoint index).  p.NCs == 0: one call.
     const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
-    wv::Mlp16ChunkParams c = {};
-    wv::Mlp16Params& q = c.p;
-    q.XQ = p.XQ; q.XK = p.XK; q.XV = p.XV; q.eta = p.eta; q.ln_w = p.ln_w; q.ln_b = p.ln_b;
-    q.W1 = p.W1; q.b1 = p.b1; q.W2 = p.W2; q.b2 = p.b2; q.W1c = p.W1c; q.b1c = p.b1c; q.W2c = p.W2c; q.b2c = p.b2c;
-    q.out = p.out; q.NH = p.NH; q.NC = p.NC; q.G = p.G; q.K = p.K; q.eps = p.eps;
-    c.step0 = step0; c.NCs = NCs;
-    c.W1f = p.W1f; c.b1f = p.b1f; c.W2f = p.W2f; c.b2f = p.b2f;
+    const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
     hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, c);
 }
 

@@ -26,6 +26,13 @@ struct ScanParams {
     float* dump;                           // DEBUG: intermediates of workgroup 0, step 0 (revision-2 forward)
 };
 
+// ScanParams begins with the fields of wv::Mlp16Params (the CS = 16 scan's arguments), in its order: the tensors, NH, NC, G, K, eps
+inline wv::Mlp16Params mlp16_params(const ScanParams& p) {
+    return {p.XQ, p.XK, p.XV, p.eta, p.ln_w, p.ln_b, p.W1, p.b1, p.W2, p.b2, p.W1c, p.b1c, p.W2c, p.b2c, p.out, p.NH, p.NC, p.G, p.K, p.eps};
+}
+static_assert(offsetof(ScanParams, eps) == offsetof(wv::Mlp16Params, eps) && offsetof(ScanParams, out) == offsetof(wv::Mlp16Params, out),
+              "ScanParams and wv::Mlp16Params list the same leading fields");
+
 bool bwd_available();
 int groups_per_chunk(const ttt_dims* d);
 // revision-2 forward scan (ttt_mfma2.hip): 8 waves per (b,h), VGPR-form MFMA, LDS transposed reads

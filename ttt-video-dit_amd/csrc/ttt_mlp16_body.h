@@ -4,9 +4,7 @@
 //   bk.wave()  wave index in the workgroup,  bk.thread() = 64 wave + lane,  bk.barrier()  workgroup barrier,
 //   bk.exp2(x), bk.rcp(x),  bk.lds_load<T>(off) / bk.lds_store<T>(off, v)  (plain LDS accesses on the device; on the emulator
 //   they feed its LDS race detector: two waves touching a word without a workgroup barrier in between is reported)
-// so that the CPU suite can execute it on the multi-wave emulator (tests/emul).  STATUS: emulator-verified against the
-// oracle; on the device it is the opt-in variant `scan16_body` of ttt_hip_debug_option until it has been timed against the
-// hand-placed kernel on an MI355X.
+// so that the CPU suite can execute it on the multi-wave emulator (tests/emul).
 #pragma once
 #include "ttt_lin16_body.h"
 

@@ -62,27 +62,92 @@ _MlpBwd = _ptr_struct("_MlpBwd", MLP_BWD_FIELDS)
 _LinFwd = _ptr_struct("_LinFwd", LIN_FWD_FIELDS)
 _LinBwd = _ptr_struct("_LinBwd", LIN_BWD_FIELDS)
 
-# TTT_HIP_ABI_VERSION of include/ttt_hip.h this binding was written against (2: return codes -3 / -10 / -11 / -12 of the TTT-MLP
-# entry points, the round-1 debug exports ttt_hip_debug_variant / _helpers gone; 3: ttt_hip_pre_backward_ld / ttt_hip_attn_pre_backward_ld,
-# ttt_hip_mlp_forward_chunk, ttt_hip_pre_forward_range / ttt_hip_post_forward_range; 4 (round 6): ttt_hip_stream_create_masked /
-# ttt_hip_stream_destroy / ttt_hip_debug_placement_probe added, the tensor entry points unchanged; 5 (round 6): the TTT-MLP forward has a
-# workspace - the ring of state records of the pair scan - and ttt_hip_mlp_forward_chunk uses its workspace arguments)
+# Tensor contract of each argument struct, keyed by its *_FIELDS names: (shape, dtype).  A shape is written in the names of
+# include/ttt_hip.h - B NH NC CS F, G = checkpoint_group_size, K = ceil(NC / G), H = 4 F - and resolved per call; dtype "act" is the
+# dtype of XQ (bf16 or fp32), "f32" / "bf16" are fixed.
+def _contract(fields, *groups):
+    spec = {name: (tuple(d if d.isalpha() else int(d) for d in shape.split()), dtype)
+            for shape, dtype, names in groups for name in names.split()}
+    assert set(spec) == set(fields) and len(spec) == len(fields), set(spec) ^ set(fields)
+    return spec
+
+
+_MLP_FWD_SPEC = _contract(
+    MLP_FWD_FIELDS,
+    ("B NH NC CS F", "act", "XQ XK XV XQW"), ("B NH NC CS 1", "act", "last_eta"), ("1 NH 1 F", "f32", "ttt_norm_weight ttt_norm_bias"),
+    ("B NH F H", "f32", "W1_init"), ("B NH 1 H", "f32", "b1_init"), ("B NH H F", "f32", "W2_init"), ("B NH 1 F", "f32", "b2_init"),
+    ("B NH K F H", "f32", "W1_checkpoints"), ("B NH K 1 H", "f32", "b1_checkpoints"),
+    ("B NH K H F", "f32", "W2_checkpoints"), ("B NH K 1 F", "f32", "b2_checkpoints"))
+_MLP_BWD_SPEC = _contract(
+    MLP_BWD_FIELDS,
+    ("B NH NC CS F", "act", "XQ XK XV XQW grad_L_XQW grad_L_XQ grad_L_XK grad_L_XV"), ("B NH NC CS 1", "act", "last_eta grad_L_last_eta"),
+    ("1 NH 1 F", "f32", "ttt_norm_weight ttt_norm_bias"), ("B NH 1 F", "f32", "grad_L_ttt_norm_weight grad_L_ttt_norm_bias"),
+    ("B NH K F H", "f32", "W1_checkpoints"), ("B NH K 1 H", "f32", "b1_checkpoints"),
+    ("B NH K H F", "f32", "W2_checkpoints"), ("B NH K 1 F", "f32", "b2_checkpoints"),
+    ("B NH G F H", "f32", "W1_init_group"), ("B NH G 1 H", "f32", "b1_init_group"),
+    ("B NH G H F", "f32", "W2_init_group"), ("B NH G 1 F", "f32", "b2_init_group"),
+    ("B NH G CS F", "bf16", "x_hat_ln_group grad_l_wrt_Z2_group x_hat_fused_group grad_x_hat_fused_group grad_output_fused_group"),
+    ("B NH G CS H", "bf16", "X2_group Z1_group Z1_bar_group X2_bar_group grad_l_wrt_Z1_group"),
+    ("B NH G CS 1", "f32", "std_ln_group std_fused_group"),
+    ("B NH F H", "f32", "grad_L_W1_last grad_L_W1_init"), ("B NH 1 H", "f32", "grad_L_b1_last grad_L_b1_init"),
+    ("B NH H F", "f32", "grad_L_W2_last grad_L_W2_init"), ("B NH 1 F", "f32", "grad_L_b2_last grad_L_b2_init"))
+# The sixteen re-materialisation buffers of the reference contract (mlp_tk.py:192-210) may be None HERE (the reference always passes
+# them; this repo's fused autograd node does not allocate what no kernel touches): the MFMA backward works in its own workspace, the
+# generic kernels need the four *_init_group buffers (the C ABI refuses NULL there).
+_MLP_BWD_SCRATCH = frozenset(MLP_BWD_FIELDS[11:27])
+_LIN_FWD_SPEC = _contract(
+    LIN_FWD_FIELDS,
+    ("B NH NC CS F", "act", "XQ XK XV XQW"), ("B NH NC CS 1", "act", "last_eta"), ("NH F", "f32", "ttt_norm_weight ttt_norm_bias"),
+    ("B NH F F", "f32", "W1_init"), ("B NH 1 F", "f32", "b1_init"),
+    ("B NH K F F", "f32", "W1_checkpoints"), ("B NH K 1 F", "f32", "b1_checkpoints"))
+_LIN_BWD_SPEC = _contract(
+    LIN_BWD_FIELDS,
+    ("B NH NC CS F", "act", "XQ XK XV grad_L_XQW grad_L_XQ grad_L_XK grad_L_XV"), ("B NH NC CS 1", "act", "last_eta grad_L_last_eta"),
+    ("NH F", "f32", "ttt_norm_weight ttt_norm_bias"), ("B NH K F F", "f32", "W1_checkpoints"), ("B NH K 1 F", "f32", "b1_checkpoints"),
+    ("B NH F F", "f32", "grad_L_W1_last grad_L_W1_init"),
+    ("B NH 1 F", "f32", "grad_L_b1_last grad_L_b1_init grad_L_ttt_norm_weight grad_L_ttt_norm_bias"),
+    ("B NH G F F", "f32", "W1_init_group"), ("B NH G 1 F", "f32", "b1_init_group"))
+
+# TTT_HIP_ABI_VERSION of include/ttt_hip.h this binding was written against (the version history is kept there)
 ABI_VERSION = 5
 
-# every extern "C" symbol declared in include/ttt_hip.h
-EXPORTED_SYMBOLS = (
-    "ttt_hip_mlp_forward_workspace", "ttt_hip_mlp_backward_workspace", "ttt_hip_linear_forward_workspace",
-    "ttt_hip_linear_backward_workspace", "ttt_hip_mlp_forward", "ttt_hip_mlp_forward_chunk", "ttt_hip_mlp_backward", "ttt_hip_linear_forward",
-    "ttt_hip_linear_backward", "ttt_hip_resolve_impl", "ttt_hip_abi_version", "ttt_hip_last_error",
-    "ttt_hip_debug_timing", "ttt_hip_debug_groups_per_chunk", "ttt_hip_debug_dump", "ttt_hip_debug_option", "ttt_hip_debug_sweep_error", "ttt_hip_sweep_error_clear", "ttt_hip_debug_occupy_cus",
-    "ttt_hip_stream_create_masked", "ttt_hip_stream_destroy", "ttt_hip_debug_placement_probe",
-    "ttt_hip_pre_forward", "ttt_hip_pre_forward_range", "ttt_hip_post_forward_range", "ttt_hip_pre_backward_partials", "ttt_hip_pre_backward", "ttt_hip_pre_backward_ld", "ttt_hip_post_partials",
-    "ttt_hip_post_forward", "ttt_hip_post_backward", "ttt_hip_gate_forward", "ttt_hip_gate_backward_partials",
-    "ttt_hip_gate_backward", "ttt_hip_attn_forward", "ttt_hip_attn_backward",
-    "ttt_hip_attn_pre_forward", "ttt_hip_attn_pre_partials", "ttt_hip_attn_pre_backward", "ttt_hip_attn_pre_backward_ld",
-    "ttt_hip_adaln_forward", "ttt_hip_adaln_backward_partials", "ttt_hip_adaln_backward",
-    "ttt_hip_resgate_forward", "ttt_hip_resgate_backward_partials", "ttt_hip_resgate_backward",
-)
+
+def _sig(args="", restype=ctypes.c_int):
+    """(restype, argtypes) from a parameter list such as "4i f 11p": [count]kind with i int / int32_t, u unsigned, l int64_t,
+    z size_t, f float, s const char*, p any other pointer (tensor data, argument struct, stream)."""
+    kinds = dict(i=ctypes.c_int, u=ctypes.c_uint, l=ctypes.c_int64, z=ctypes.c_size_t, f=ctypes.c_float, s=ctypes.c_char_p, p=ctypes.c_void_p)
+    return restype, [kinds[a[-1]] for a in args.split() for _ in range(int(a[:-1] or 1))]
+
+
+# Prototype of every extern "C" symbol declared in include/ttt_hip.h (tests/test_abi_cpu.py compares the two); load_library() applies
+# them, so that ctypes converts - and refuses - arguments by the declared parameter types.
+_SCAN = _sig("3p z p")                          # dims, args, workspace, workspace_bytes, stream
+_PROTOTYPES = {
+    **{f"ttt_hip_{op}_workspace": _sig("p", ctypes.c_size_t) for op in ("mlp_forward", "mlp_backward", "linear_forward", "linear_backward")},
+    "ttt_hip_mlp_forward": _SCAN, "ttt_hip_mlp_backward": _SCAN, "ttt_hip_linear_forward": _SCAN, "ttt_hip_linear_backward": _SCAN,
+    "ttt_hip_mlp_forward_chunk": _sig("2p 2i 5p z p"),
+    "ttt_hip_resolve_impl": _sig("p 2i"), "ttt_hip_abi_version": _sig(), "ttt_hip_last_error": _sig("", ctypes.c_char_p),
+    # debug knobs, sweep error word, CU-masked streams
+    "ttt_hip_debug_timing": _sig("p", None), "ttt_hip_debug_dump": _sig("p", None),
+    "ttt_hip_debug_groups_per_chunk": _sig("i", None), "ttt_hip_debug_option": _sig("s i"),
+    "ttt_hip_debug_sweep_error": _sig("", ctypes.c_uint), "ttt_hip_sweep_error_clear": _sig("", None),
+    "ttt_hip_debug_occupy_cus": _sig("3i p"), "ttt_hip_debug_placement_probe": _sig("p 3i p"),
+    "ttt_hip_stream_create_masked": _sig("p i p"), "ttt_hip_stream_destroy": _sig("p"),
+    # fused pre / post / gate of the TTT layer: B, L, NH, F (gate: B, L, D, n_text) first, the stream last
+    "ttt_hip_pre_forward": _sig("4i 12p"), "ttt_hip_pre_forward_range": _sig("4i 11p 2i p"),
+    "ttt_hip_pre_backward": _sig("4i 16p"), "ttt_hip_pre_backward_ld": _sig("4i 13p l 3p"), "ttt_hip_pre_backward_partials": _sig("i"),
+    "ttt_hip_post_forward": _sig("4i f 6p"), "ttt_hip_post_forward_range": _sig("4i f 5p 2i p"),
+    "ttt_hip_post_backward": _sig("4i f 8p"), "ttt_hip_post_partials": _sig("2i"),
+    "ttt_hip_gate_forward": _sig("4i 6p"), "ttt_hip_gate_backward": _sig("4i 7p"), "ttt_hip_gate_backward_partials": _sig("i"),
+    # segment attention (argument struct, stream) and its fused LayerNorm + RoPE: B, S, NH, n_text, eps first
+    "ttt_hip_attn_forward": _sig("2p"), "ttt_hip_attn_backward": _sig("2p"),
+    "ttt_hip_attn_pre_forward": _sig("4i f 11p"), "ttt_hip_attn_pre_partials": _sig("3i"),
+    "ttt_hip_attn_pre_backward": _sig("4i f 12p"), "ttt_hip_attn_pre_backward_ld": _sig("4i f 10p l 2p"),
+    # TransformerLayer glue: B, Lt, Lv, D first
+    "ttt_hip_adaln_forward": _sig("4i f 8p"), "ttt_hip_adaln_backward": _sig("4i f 10p"), "ttt_hip_adaln_backward_partials": _sig(),
+    "ttt_hip_resgate_forward": _sig("4i 7p"), "ttt_hip_resgate_backward": _sig("4i 7p"), "ttt_hip_resgate_backward_partials": _sig("i"),
+}
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -92,7 +157,8 @@ def library_path() -> str:
 
 
 def load_library() -> ctypes.CDLL:
-    """dlopen libttt_hip.so (built by ``__graft_entry__.build()`` / ``csrc/build.sh``).  Raises if absent."""
+    """dlopen libttt_hip.so (built by ``__graft_entry__.build()`` / ``csrc/build.sh``) and give every exported function its prototype.
+    Raises if absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -101,57 +167,47 @@ def load_library() -> ctypes.CDLL:
             f"test_time_training: HIP library not found at {_LIB_PATH}; build it with "
             f"`python -c 'import __graft_entry__ as g; g.build()'` (there is no CPU fallback)")
     lib = ctypes.CDLL(_LIB_PATH)
-    for n in ("mlp_forward", "mlp_backward", "linear_forward", "linear_backward"):
-        getattr(lib, f"ttt_hip_{n}_workspace").restype = ctypes.c_size_t
-        getattr(lib, f"ttt_hip_{n}_workspace").argtypes = [ctypes.c_void_p]
-        getattr(lib, f"ttt_hip_{n}").restype = ctypes.c_int
-        getattr(lib, f"ttt_hip_{n}").argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.ttt_hip_resolve_impl.restype = ctypes.c_int
-    lib.ttt_hip_resolve_impl.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    lib.ttt_hip_abi_version.restype = ctypes.c_int
-    lib.ttt_hip_last_error.restype = ctypes.c_char_p
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
 
+def _p(t: Optional[torch.Tensor]):
+    """device pointer of a tensor, or None (a null pointer) for None"""
+    return t.data_ptr() if t is not None else None
+
+
 def debug_timing(buf: Optional[torch.Tensor]) -> None:
     """DEBUG: per-phase cycle counters of workgroup 0 are accumulated into ``buf`` (16 x int64, zeroed, on device)."""
-    lib = load_library()
-    lib.ttt_hip_debug_timing.argtypes = [ctypes.c_void_p]
-    lib.ttt_hip_debug_timing(buf.data_ptr() if buf is not None else None)
+    load_library().ttt_hip_debug_timing(_p(buf))
+
+
+def debug_option(name: str, value: int) -> None:
+    """DEBUG / A-B knobs by name, described at ttt_hip_debug_option in include/ttt_hip.h: ``groups_per_chunk``, ``overlap_tail``,
+    ``fast_records``, ``sweep_fast_count`` (a query: see ``sweep_fast_count()``), ``deriver_split``, ``attn_prio``, ``scan_pair`` and the
+    fault injections ``sweep_fault``, ``scan_fault``."""
+    if load_library().ttt_hip_debug_option(name.encode(), int(value)) != 0:
+        raise ValueError(f"unknown debug option {name!r}")
 
 
 def debug_groups_per_chunk(groups: int) -> None:
     """DEBUG: force the MFMA backward's chunk size in checkpoint groups (0 = automatic)."""
-    lib = load_library()
-    lib.ttt_hip_debug_groups_per_chunk.argtypes = [ctypes.c_int]
-    lib.ttt_hip_debug_groups_per_chunk(int(groups))
-
-
-def debug_option(name: str, value: int) -> None:
-    """DEBUG / A-B knobs by name (see ttt_hip_debug_option in include/ttt_hip.h): ``groups_per_chunk``, ``fast_records``."""
-    lib = load_library()
-    lib.ttt_hip_debug_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
-    lib.ttt_hip_debug_option.restype = ctypes.c_int
-    if lib.ttt_hip_debug_option(name.encode(), int(value)) != 0:
-        raise ValueError(f"unknown debug option {name!r}")
+    debug_option("groups_per_chunk", groups)
 
 
 def sweep_error() -> int:
     """0, or 1 + (b,h) of a cluster-form backward workgroup whose hand-over partner never arrived (synchronises)."""
-    lib = load_library()
-    lib.ttt_hip_debug_sweep_error.restype = ctypes.c_uint
-    return int(lib.ttt_hip_debug_sweep_error())
+    return int(load_library().ttt_hip_debug_sweep_error())
 
 
 def debug_occupy_cus(workgroups: int, lds_bytes: int, microseconds: int, stream=None) -> None:
     """DEBUG (stress tests): hold ``workgroups`` CUs' worth of LDS for ``microseconds`` on ``stream`` (default: the current one)."""
-    lib = load_library()
     st = (stream or torch.cuda.current_stream()).cuda_stream
-    lib.ttt_hip_debug_occupy_cus.restype = ctypes.c_int
-    if lib.ttt_hip_debug_occupy_cus(int(workgroups), int(lds_bytes), int(microseconds), ctypes.c_void_p(st)) != 0:
+    if load_library().ttt_hip_debug_occupy_cus(int(workgroups), int(lds_bytes), int(microseconds), st) != 0:
         raise RuntimeError("ttt_hip_debug_occupy_cus: bad arguments or launch failure")
 
 
@@ -163,9 +219,7 @@ def masked_stream(cu_mask_words) -> "torch.cuda.ExternalStream":
     words = [int(w) & 0xFFFFFFFF for w in cu_mask_words]
     arr = (ctypes.c_uint * len(words))(*words)
     out = ctypes.c_void_p()
-    lib.ttt_hip_stream_create_masked.restype = ctypes.c_int
     if lib.ttt_hip_stream_create_masked(arr, len(words), ctypes.byref(out)) != 0:
-        lib.ttt_hip_last_error.restype = ctypes.c_char_p
         raise RuntimeError(lib.ttt_hip_last_error().decode())
     return torch.cuda.ExternalStream(out.value)
 
@@ -176,9 +230,8 @@ def placement_probe(workgroups: int, stream=None, lds_bytes: int = 150 * 1024, m
     lib = load_library()
     st = stream or torch.cuda.current_stream()
     out = torch.zeros(workgroups, dtype=torch.int32, device="cuda")
-    lib.ttt_hip_debug_placement_probe.restype = ctypes.c_int
     with torch.cuda.stream(st):
-        rc = lib.ttt_hip_debug_placement_probe(ctypes.c_void_p(out.data_ptr()), int(workgroups), int(lds_bytes), int(microseconds), ctypes.c_void_p(st.cuda_stream))
+        rc = lib.ttt_hip_debug_placement_probe(out.data_ptr(), int(workgroups), int(lds_bytes), int(microseconds), st.cuda_stream)
     if rc != 0:
         raise RuntimeError("ttt_hip_debug_placement_probe: bad arguments or launch failure")
     st.synchronize()
@@ -193,17 +246,12 @@ def sweep_error_clear() -> None:
 
 def sweep_fast_count() -> int:
     """DEBUG statistic: cluster workgroup launches that proved same-XCD placement and published plain (L2-resident) records."""
-    lib = load_library()
-    lib.ttt_hip_debug_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
-    lib.ttt_hip_debug_option.restype = ctypes.c_int
-    return -2 - int(lib.ttt_hip_debug_option(b"sweep_fast_count", 0))
+    return -2 - int(load_library().ttt_hip_debug_option(b"sweep_fast_count", 0))
 
 
 def debug_dump(buf: Optional[torch.Tensor]) -> None:
     """DEBUG: step-0 intermediates of workgroup 0 of the revision-2 forward go to ``buf`` (>= 120000 fp32 on device)."""
-    lib = load_library()
-    lib.ttt_hip_debug_dump.argtypes = [ctypes.c_void_p]
-    lib.ttt_hip_debug_dump(buf.data_ptr() if buf is not None else None)
+    load_library().ttt_hip_debug_dump(_p(buf))
 
 
 def set_impl(name: str) -> None:
@@ -283,14 +331,14 @@ def release_workspaces() -> None:
     _ws_cache.clear()
 
 
-def _launch(fn_name: str, dims: _Dims, args, device) -> None:
+def _launch(fn_name: str, dims: _Dims, args, device, suffix: str = "", extra=()) -> None:
+    """``fn_name + suffix``(dims, args, *extra, workspace, workspace_bytes, stream) with the workspace ``fn_name`` asks for"""
     lib = load_library()
     ws_bytes = getattr(lib, fn_name + "_workspace")(ctypes.byref(dims))
     stream = torch.cuda.current_stream(device).cuda_stream
     ws = _workspace(device, stream, ws_bytes) if ws_bytes else None
     with torch.cuda.device(device):
-        rc = getattr(lib, fn_name)(ctypes.byref(dims), ctypes.byref(args), ws.data_ptr() if ws is not None else None,
-                                   ws_bytes, ctypes.c_void_p(stream))
+        rc = getattr(lib, fn_name + suffix)(ctypes.byref(dims), ctypes.byref(args), *extra, _p(ws), ws_bytes, stream)
     if rc != 0:
         raise RuntimeError(lib.ttt_hip_last_error().decode())
 
@@ -304,27 +352,36 @@ def resolved_impl(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, mlp=True, backw
 
 
 # ------------------------------------------------------------------------------------------------
-def ttt_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
-                W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch, checkpoint_group_size):
-    """TTT-MLP forward scan; argument list of the reference call site mlp_tk.py:116-133."""
+def _fill_args(struct, spec, tensors, sizes, act, optional=()):
+    """Check ``tensors`` (in the order of the struct's fields) against their contract ``spec`` at the dimensions ``sizes`` (a dict
+    B .. H) and activation dtype ``act``; return the filled argument struct.  A field named in ``optional`` may be None (a null pointer)."""
+    dtypes = {"act": act, "f32": torch.float32, "bf16": torch.bfloat16}
+    ptrs = []
+    for (name, _), t in zip(struct._fields_, tensors):
+        if t is not None or name not in optional:
+            shape, dtype = spec[name]
+            _check(t, name, [sizes.get(d, d) for d in shape], dtypes[dtype])
+        ptrs.append(_p(t))
+    return struct(*ptrs)
+
+
+def _scan_args(struct, spec, tensors, checkpoint_group_size, optional=()):
+    """(dims, args, device) of one scan op for ``_launch``: the sizes are XQ's, the tensors are checked against ``spec``"""
+    XQ = tensors[0]
     _check5(XQ)
     B, NH, NC, CS, F = XQ.shape
     G = int(checkpoint_group_size)
-    K = -(-NC // G)
-    H = 4 * F
-    act, f32 = XQ.dtype, torch.float32
-    t = dict(XQ=XQ, XK=XK, XV=XV, last_eta=last_eta, ttt_norm_weight=ttt_norm_weight, ttt_norm_bias=ttt_norm_bias,
-             W1_init=W1_init, b1_init=b1_init, W2_init=W2_init, b2_init=b2_init, W1_checkpoints=W1_checkpoints,
-             b1_checkpoints=b1_checkpoints, W2_checkpoints=W2_checkpoints, b2_checkpoints=b2_checkpoints, XQW=XQW_batch)
-    spec = dict(XQ=((B, NH, NC, CS, F), act), XK=((B, NH, NC, CS, F), act), XV=((B, NH, NC, CS, F), act),
-                last_eta=((B, NH, NC, CS, 1), act), ttt_norm_weight=((1, NH, 1, F), f32), ttt_norm_bias=((1, NH, 1, F), f32),
-                W1_init=((B, NH, F, H), f32), b1_init=((B, NH, 1, H), f32), W2_init=((B, NH, H, F), f32),
-                b2_init=((B, NH, 1, F), f32), W1_checkpoints=((B, NH, K, F, H), f32), b1_checkpoints=((B, NH, K, 1, H), f32),
-                W2_checkpoints=((B, NH, K, H, F), f32), b2_checkpoints=((B, NH, K, 1, F), f32), XQW=((B, NH, NC, CS, F), act))
-    for k, (shape, dt) in spec.items():
-        _check(t[k], k, shape, dt)
-    args = _MlpFwd(*[t[k].data_ptr() for k in MLP_FWD_FIELDS])
-    _launch("ttt_hip_mlp_forward", _dims(B, NH, NC, CS, F, G, act), args, XQ.device)
+    sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
+    args = _fill_args(struct, spec, tensors, sizes, XQ.dtype, optional)
+    return _dims(B, NH, NC, CS, F, G, XQ.dtype), args, XQ.device
+
+
+def ttt_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
+                W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch, checkpoint_group_size):
+    """TTT-MLP forward scan; argument list of the reference call site mlp_tk.py:116-133."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
+               W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch)
+    _launch("ttt_hip_mlp_forward", *_scan_args(_MlpFwd, _MLP_FWD_SPEC, tensors, checkpoint_group_size))
 
 
 def ttt_forward_chunk(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W2_state, b2_state,
@@ -334,34 +391,12 @@ def ttt_forward_chunk(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_s
     ([B,NH,F,H], [B,NH,1,H], [B,NH,H,F], [B,NH,1,F]), which it REPLACES by the state after its last step, so that consecutive
     calls walk the sequence with the bits of the one-call forward.  MFMA scan only.  At mini-batches of 64 parts start and end at
     checkpoint-group boundaries (or at the end); at mini-batches of 16 a part is any [step0, step0 + nsteps) inside [0, NC)."""
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    K = -(-NC // G)
-    H = 4 * F
-    act, f32 = XQ.dtype, torch.float32
-    t = dict(XQ=XQ, XK=XK, XV=XV, last_eta=last_eta, ttt_norm_weight=ttt_norm_weight, ttt_norm_bias=ttt_norm_bias,
-             W1_init=W1_state, b1_init=b1_state, W2_init=W2_state, b2_init=b2_state, W1_checkpoints=W1_checkpoints,
-             b1_checkpoints=b1_checkpoints, W2_checkpoints=W2_checkpoints, b2_checkpoints=b2_checkpoints, XQW=XQW_batch)
-    spec = dict(XQ=((B, NH, NC, CS, F), act), XK=((B, NH, NC, CS, F), act), XV=((B, NH, NC, CS, F), act),
-                last_eta=((B, NH, NC, CS, 1), act), ttt_norm_weight=((1, NH, 1, F), f32), ttt_norm_bias=((1, NH, 1, F), f32),
-                W1_init=((B, NH, F, H), f32), b1_init=((B, NH, 1, H), f32), W2_init=((B, NH, H, F), f32),
-                b2_init=((B, NH, 1, F), f32), W1_checkpoints=((B, NH, K, F, H), f32), b1_checkpoints=((B, NH, K, 1, H), f32),
-                W2_checkpoints=((B, NH, K, H, F), f32), b2_checkpoints=((B, NH, K, 1, F), f32), XQW=((B, NH, NC, CS, F), act))
-    for k, (shape, dt) in spec.items():
-        _check(t[k], k, shape, dt)
-    args = _MlpFwd(*[t[k].data_ptr() for k in MLP_FWD_FIELDS])
-    dims = _dims(B, NH, NC, CS, F, G, act)
-    lib = load_library()
-    stream = torch.cuda.current_stream(XQ.device).cuda_stream
-    ws_bytes = lib.ttt_hip_mlp_forward_workspace(ctypes.byref(dims))       # the pair scan's ring of state records (round 6)
-    ws = _workspace(XQ.device, stream, ws_bytes) if ws_bytes else None
-    with torch.cuda.device(XQ.device):
-        rc = lib.ttt_hip_mlp_forward_chunk(ctypes.byref(dims), ctypes.byref(args), ctypes.c_int(int(step0)), ctypes.c_int(int(nsteps)),
-                                           _p(W1_state), _p(b1_state), _p(W2_state), _p(b2_state), ctypes.c_void_p(ws.data_ptr() if ws is not None else None),
-                                           ctypes.c_size_t(ws_bytes), ctypes.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W2_state, b2_state,
+               W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_MlpFwd, _MLP_FWD_SPEC, tensors, checkpoint_group_size)
+    # the workspace is ttt_forward's (the pair scan's ring of state records); the final state goes where the initial one came from
+    _launch("ttt_hip_mlp_forward", dims, args, device, suffix="_chunk",
+            extra=(int(step0), int(nsteps), args.W1_init, args.b1_init, args.W2_init, args.b2_init))
 
 
 def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
@@ -372,69 +407,21 @@ def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkp
                  grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
                  grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
     """TTT-MLP backward; the 42 tensors + 1 int of the reference call site mlp_tk.py:227-275."""
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    K = -(-NC // G)
-    H = 4 * F
-    act, f32, bf = XQ.dtype, torch.float32, torch.bfloat16
-    vals = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
-            b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
-            std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
-            x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
-            grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
-            grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
-            grad_L_XQ, grad_L_XK, grad_L_XV)
-    t = dict(zip(MLP_BWD_FIELDS, vals))
-    A = ((B, NH, NC, CS, F), act)
-    spec = dict(XQ=A, XK=A, XV=A, last_eta=((B, NH, NC, CS, 1), act),
-                ttt_norm_weight=((1, NH, 1, F), f32), ttt_norm_bias=((1, NH, 1, F), f32),
-                W1_checkpoints=((B, NH, K, F, H), f32), b1_checkpoints=((B, NH, K, 1, H), f32),
-                W2_checkpoints=((B, NH, K, H, F), f32), b2_checkpoints=((B, NH, K, 1, F), f32), XQW=A,
-                W1_init_group=((B, NH, G, F, H), f32), b1_init_group=((B, NH, G, 1, H), f32),
-                W2_init_group=((B, NH, G, H, F), f32), b2_init_group=((B, NH, G, 1, F), f32),
-                x_hat_ln_group=((B, NH, G, CS, F), bf), std_ln_group=((B, NH, G, CS, 1), f32),
-                X2_group=((B, NH, G, CS, H), bf), Z1_group=((B, NH, G, CS, H), bf), Z1_bar_group=((B, NH, G, CS, H), bf),
-                X2_bar_group=((B, NH, G, CS, H), bf), grad_l_wrt_Z2_group=((B, NH, G, CS, F), bf),
-                grad_l_wrt_Z1_group=((B, NH, G, CS, H), bf), x_hat_fused_group=((B, NH, G, CS, F), bf),
-                grad_x_hat_fused_group=((B, NH, G, CS, F), bf), grad_output_fused_group=((B, NH, G, CS, F), bf),
-                std_fused_group=((B, NH, G, CS, 1), f32),
-                grad_L_W1_last=((B, NH, F, H), f32), grad_L_b1_last=((B, NH, 1, H), f32),
-                grad_L_W2_last=((B, NH, H, F), f32), grad_L_b2_last=((B, NH, 1, F), f32), grad_L_XQW=A,
-                grad_L_ttt_norm_weight=((B, NH, 1, F), f32), grad_L_ttt_norm_bias=((B, NH, 1, F), f32),
-                grad_L_W1_init=((B, NH, F, H), f32), grad_L_b1_init=((B, NH, 1, H), f32),
-                grad_L_W2_init=((B, NH, H, F), f32), grad_L_b2_init=((B, NH, 1, F), f32),
-                grad_L_last_eta=((B, NH, NC, CS, 1), act), grad_L_XQ=A, grad_L_XK=A, grad_L_XV=A)
-    # The sixteen re-materialisation buffers of the reference contract (mlp_tk.py:192-210) may be None HERE (the reference
-    # always passes them; this repo's fused autograd node does not allocate what no kernel touches): the MFMA backward works in
-    # its own workspace, the generic kernels need the four *_init_group buffers (the C ABI refuses NULL there).
-    scratch = MLP_BWD_FIELDS[11:27]
-    for k, (shape, dt) in spec.items():
-        if k in scratch and t[k] is None:
-            continue
-        _check(t[k], k, shape, dt)
-    args = _MlpBwd(*[(t[k].data_ptr() if t[k] is not None else None) for k in MLP_BWD_FIELDS])
-    _launch("ttt_hip_mlp_backward", _dims(B, NH, NC, CS, F, G, act), args, XQ.device)
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+               b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+               std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+               x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+               grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+               grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+               grad_L_XQ, grad_L_XK, grad_L_XV)
+    _launch("ttt_hip_mlp_backward", *_scan_args(_MlpBwd, _MLP_BWD_SPEC, tensors, checkpoint_group_size, optional=_MLP_BWD_SCRATCH))
 
 
 def ttt_linear_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,
                        b1_checkpoints, XQW_batch, checkpoint_group_size):
     """TTT-Linear forward scan (replaces ttt_linear_scan_forward, linear_triton.py:98-129)."""
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    K = -(-NC // G)
-    act, f32 = XQ.dtype, torch.float32
-    vals = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints, b1_checkpoints, XQW_batch)
-    t = dict(zip(LIN_FWD_FIELDS, vals))
-    A = ((B, NH, NC, CS, F), act)
-    spec = dict(XQ=A, XK=A, XV=A, last_eta=((B, NH, NC, CS, 1), act), ttt_norm_weight=((NH, F), f32),
-                ttt_norm_bias=((NH, F), f32), W1_init=((B, NH, F, F), f32), b1_init=((B, NH, 1, F), f32),
-                W1_checkpoints=((B, NH, K, F, F), f32), b1_checkpoints=((B, NH, K, 1, F), f32), XQW=A)
-    for k, (shape, dt) in spec.items():
-        _check(t[k], k, shape, dt)
-    args = _LinFwd(*[t[k].data_ptr() for k in LIN_FWD_FIELDS])
-    _launch("ttt_hip_linear_forward", _dims(B, NH, NC, CS, F, G, act), args, XQ.device)
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints, b1_checkpoints, XQW_batch)
+    _launch("ttt_hip_linear_forward", *_scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size))
 
 
 def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
@@ -442,48 +429,37 @@ def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1
                         grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
                         grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
     """TTT-Linear backward (replaces ttt_linear_scan_backward, linear_triton.py:203-246)."""
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    K = -(-NC // G)
-    act, f32 = XQ.dtype, torch.float32
-    vals = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last,
-            grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias,
-            grad_L_W1_init, grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    t = dict(zip(LIN_BWD_FIELDS, vals))
-    A = ((B, NH, NC, CS, F), act)
-    spec = dict(XQ=A, XK=A, XV=A, last_eta=((B, NH, NC, CS, 1), act), ttt_norm_weight=((NH, F), f32),
-                ttt_norm_bias=((NH, F), f32), W1_checkpoints=((B, NH, K, F, F), f32), b1_checkpoints=((B, NH, K, 1, F), f32),
-                grad_L_W1_last=((B, NH, F, F), f32), grad_L_b1_last=((B, NH, 1, F), f32), grad_L_XQW=A,
-                W1_init_group=((B, NH, G, F, F), f32), b1_init_group=((B, NH, G, 1, F), f32),
-                grad_L_ttt_norm_weight=((B, NH, 1, F), f32), grad_L_ttt_norm_bias=((B, NH, 1, F), f32),
-                grad_L_W1_init=((B, NH, F, F), f32), grad_L_b1_init=((B, NH, 1, F), f32),
-                grad_L_last_eta=((B, NH, NC, CS, 1), act), grad_L_XQ=A, grad_L_XK=A, grad_L_XV=A)
-    for k, (shape, dt) in spec.items():
-        _check(t[k], k, shape, dt)
-    args = _LinBwd(*[t[k].data_ptr() for k in LIN_BWD_FIELDS])
-    _launch("ttt_hip_linear_backward", _dims(B, NH, NC, CS, F, G, act), args, XQ.device)
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last,
+               grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias,
+               grad_L_W1_init, grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    _launch("ttt_hip_linear_backward", *_scan_args(_LinBwd, _LIN_BWD_SPEC, tensors, checkpoint_group_size))
 
 
 # ------------------------------------------------------------------------------------------------
 # Fused pre- / post-processing kernels (include/ttt_hip.h, "Fused pre- / post-processing").  Thin wrappers: the
 # caller (ttt_amd/models/ssm/fused.py) allocates every tensor; bf16 activations, fp32 parameters / tables.
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+def _req(dtype, **tensors):
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on a HIP device")
 
 
-def _req(t, name, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError(f"{name}: expected a contiguous {dtype} tensor on a HIP device")
+def _req_rows(ld, shape, **tensors):
+    """bf16 [B, L, D] tensors on a HIP device: contiguous (``ld`` None), or with token rows ``ld`` elements apart (column blocks of a
+    wider buffer)"""
+    if ld is None:
+        return _req(torch.bfloat16, **tensors)
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != tuple(shape) \
+                or t.stride(2) != 1 or t.stride(1) != ld or (shape[0] > 1 and t.stride(0) != shape[1] * ld) or t.data_ptr() % 16:
+            raise RuntimeError(f"{name}: expected a bf16 {tuple(shape)} tensor on a HIP device with token rows {ld} elements apart")
 
 
 def _call(fn, *args, device):
+    """``fn``(*args, stream) on the current stream of ``device``"""
     lib = load_library()
-    f = getattr(lib, fn)
-    f.restype = ctypes.c_int
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     with torch.cuda.device(device):
-        rc = f(*args, stream)
+        rc = getattr(lib, fn)(*args, torch.cuda.current_stream(device).cuda_stream)
     if rc != 0:
         raise RuntimeError(lib.ttt_hip_last_error().decode())
 
@@ -499,12 +475,12 @@ def _req_maps(rope, src, pos, L, F, n_pos):
     for t, n in ((src, "src"), (pos, "pos")):
         if t is None:
             continue
-        _req(t, n, torch.int32)
+        _req(torch.int32, **{n: t})
         if t.numel() != L:
             raise RuntimeError(f"{n}: expected {L} entries, got {t.numel()}")
     if rope is None:
         return
-    _req(rope, "rope", torch.float32)
+    _req(torch.float32, rope=rope)
     if rope.numel() % F != 0:
         raise RuntimeError(f"rope: expected [n_pos, {F // 2}, 2] (cos, sin) pairs, got {tuple(rope.shape)}")
     n_rows = rope.numel() // F
@@ -527,10 +503,8 @@ def pre_forward(XQ_raw, XK_raw, XV_raw, rope, src, pos, ln_w, ln_b, XQ, XK, XV, 
     """``t0``, ``tn``: the scan positions [t0, t0 + tn) only (a part of the sequence; default: all of it)"""
     B, L, D = XQ_raw.shape
     _req_maps(rope, src, pos, L, D // NH, n_pos)
-    for t, n in ((XQ_raw, "XQ_raw"), (XK_raw, "XK_raw"), (XV_raw, "XV_raw"), (XQ, "XQ"), (XK, "XK"), (XV, "XV")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((ln_w, "ln_w"), (ln_b, "ln_b")):
-        _req(t, n, torch.float32)
+    _req(torch.bfloat16, XQ_raw=XQ_raw, XK_raw=XK_raw, XV_raw=XV_raw, XQ=XQ, XK=XK, XV=XV)
+    _req(torch.float32, ln_w=ln_w, ln_b=ln_b)
     _call("ttt_hip_pre_forward_range", B, L, NH, D // NH, _p(XQ_raw), _p(XK_raw), _p(XV_raw), _p(rope), _p(src), _p(pos), _p(ln_w), _p(ln_b),
           _p(XQ), _p(XK), _p(XV), int(t0), int(L - t0 if tn is None else tn), device=XQ_raw.device)
 
@@ -539,29 +513,17 @@ def pre_backward_partials(NH):
     return load_library().ttt_hip_pre_backward_partials(int(NH))
 
 
-def _req_rows(t, name, shape, ld):
-    """a bf16 [B, L, D] tensor on a HIP device whose token rows are `ld` elements apart (a column block of a wider buffer)"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != tuple(shape) \
-            or t.stride(2) != 1 or t.stride(1) != ld or (shape[0] > 1 and t.stride(0) != shape[1] * ld) or t.data_ptr() % 16:
-        raise RuntimeError(f"{name}: expected a bf16 {tuple(shape)} tensor on a HIP device with token rows {ld} elements apart")
-
-
 def pre_backward(XQ_raw, XK_raw, XV_raw, rope, src, pos, ln_w, dXQ, dXK, dXV, dXQ_raw, dXK_raw, dXV_raw, dlnw_part, dlnb_part, NH, ld_out=None):
     """``ld_out``: row stride (elements) of the three raw-gradient outputs - None: contiguous [B, L, D] tensors; 3 * D: the column
     blocks of one [B, L, 3 D] buffer (the q / k / v projections' weight gradients are then one GEMM, ttt_amd/infra/fused_linear.py)."""
     B, L, D = XQ_raw.shape
-    for t, n in ((XQ_raw, "XQ_raw"), (XK_raw, "XK_raw"), (XV_raw, "XV_raw"), (dXQ, "dXQ"), (dXK, "dXK"), (dXV, "dXV")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((dXQ_raw, "dXQ_raw"), (dXK_raw, "dXK_raw"), (dXV_raw, "dXV_raw")):
-        if ld_out is None:
-            _req(t, n, torch.bfloat16)
-        else:
-            _req_rows(t, n, (B, L, D), int(ld_out))
-    for t, n in ((ln_w, "ln_w"), (dlnw_part, "dlnw_part"), (dlnb_part, "dlnb_part")):
-        _req(t, n, torch.float32)
+    ld = None if ld_out is None else int(ld_out)
+    _req(torch.bfloat16, XQ_raw=XQ_raw, XK_raw=XK_raw, XV_raw=XV_raw, dXQ=dXQ, dXK=dXK, dXV=dXV)
+    _req_rows(ld, (B, L, D), dXQ_raw=dXQ_raw, dXK_raw=dXK_raw, dXV_raw=dXV_raw)
+    _req(torch.float32, ln_w=ln_w, dlnw_part=dlnw_part, dlnb_part=dlnb_part)
     _call("ttt_hip_pre_backward_ld", B, L, NH, D // NH, _p(XQ_raw), _p(XK_raw), _p(XV_raw), _p(rope), _p(src), _p(pos), _p(ln_w),
-          _p(dXQ), _p(dXK), _p(dXV), _p(dXQ_raw), _p(dXK_raw), _p(dXV_raw), ctypes.c_int64(D if ld_out is None else int(ld_out)),
-          _p(dlnw_part), _p(dlnb_part), device=XQ_raw.device)
+          _p(dXQ), _p(dXK), _p(dXV), _p(dXQ_raw), _p(dXK_raw), _p(dXV_raw), D if ld is None else ld, _p(dlnw_part), _p(dlnb_part),
+          device=XQ_raw.device)
 
 
 def post_partials(B, L):
@@ -571,23 +533,23 @@ def post_partials(B, L):
 def post_forward(Y, src, w, b, out, eps, t0=0, tn=None):
     """``t0``, ``tn``: the scan positions [t0, t0 + tn) only (default: all)"""
     B, NH, L, F = Y.shape
-    _req(Y, "Y", torch.bfloat16); _req(out, "out", torch.bfloat16); _req(w, "w", torch.float32); _req(b, "b", torch.float32)
-    _call("ttt_hip_post_forward_range", B, L, NH, F, ctypes.c_float(eps), _p(Y), _p(src), _p(w), _p(b), _p(out),
+    _req(torch.bfloat16, Y=Y, out=out)
+    _req(torch.float32, w=w, b=b)
+    _call("ttt_hip_post_forward_range", B, L, NH, F, eps, _p(Y), _p(src), _p(w), _p(b), _p(out),
           int(t0), int(L - t0 if tn is None else tn), device=Y.device)
 
 
 def post_backward(Y, dOut, src, w, dY, dw_part, db_part, eps):
     B, NH, L, F = Y.shape
-    _req(Y, "Y", torch.bfloat16); _req(dOut, "dOut", torch.bfloat16); _req(dY, "dY", torch.bfloat16)
-    _req(w, "w", torch.float32); _req(dw_part, "dw_part", torch.float32); _req(db_part, "db_part", torch.float32)
-    _call("ttt_hip_post_backward", B, L, NH, F, ctypes.c_float(eps), _p(Y), _p(dOut), _p(src), _p(w), _p(dY), _p(dw_part), _p(db_part),
-          device=Y.device)
+    _req(torch.bfloat16, Y=Y, dOut=dOut, dY=dY)
+    _req(torch.float32, w=w, dw_part=dw_part, db_part=db_part)
+    _call("ttt_hip_post_backward", B, L, NH, F, eps, _p(Y), _p(dOut), _p(src), _p(w), _p(dY), _p(dw_part), _p(db_part), device=Y.device)
 
 
 def gate_forward(res, y, tanh_text, tanh_video, out, n_text):
     B, L, D = res.shape
-    _req(res, "res", torch.bfloat16); _req(y, "y", torch.bfloat16); _req(out, "out", torch.bfloat16)
-    _req(tanh_text, "tanh_text", torch.float32); _req(tanh_video, "tanh_video", torch.float32)
+    _req(torch.bfloat16, res=res, y=y, out=out)
+    _req(torch.float32, tanh_text=tanh_text, tanh_video=tanh_video)
     _call("ttt_hip_gate_forward", B, L, D, int(n_text), _p(res), _p(y), _p(tanh_text), _p(tanh_video), _p(out), device=res.device)
 
 
@@ -597,8 +559,8 @@ def gate_backward_partials(D):
 
 def gate_backward(g, y, tanh_text, tanh_video, dy, dtanh_part, n_text):
     B, L, D = g.shape
-    _req(g, "g", torch.bfloat16); _req(y, "y", torch.bfloat16); _req(dy, "dy", torch.bfloat16)
-    _req(tanh_text, "tanh_text", torch.float32); _req(tanh_video, "tanh_video", torch.float32); _req(dtanh_part, "dtanh_part", torch.float32)
+    _req(torch.bfloat16, g=g, y=y, dy=dy)
+    _req(torch.float32, tanh_text=tanh_text, tanh_video=tanh_video, dtanh_part=dtanh_part)
     _call("ttt_hip_gate_backward", B, L, D, int(n_text), _p(g), _p(y), _p(tanh_text), _p(tanh_video), _p(dy), _p(dtanh_part), device=g.device)
 
 
@@ -632,17 +594,18 @@ def _attn_tensor(t, name, shape):
 def attn_forward(q, k, v, out, lse, scale):
     """O = softmax(q k^T * scale) v for [B, NH, S, 64] bf16 views (any batch/head/token strides); lse [B,NH,S] fp32 or None."""
     B, NH, S, D = q.shape
-    a = _AttnFwd(_attn_tensor(q, "q", (B, NH, S, D)), _attn_tensor(k, "k", (B, NH, S, D)), _attn_tensor(v, "v", (B, NH, S, D)),
-                 _attn_tensor(out, "out", (B, NH, S, D)), lse.data_ptr() if lse is not None else None, B, NH, S, D, float(scale))
+    sh = (B, NH, S, D)
+    a = _AttnFwd(_attn_tensor(q, "q", sh), _attn_tensor(k, "k", sh), _attn_tensor(v, "v", sh), _attn_tensor(out, "out", sh),
+                 _p(lse), B, NH, S, D, float(scale))
     if lse is not None:
-        _req(lse, "lse", torch.float32)
+        _req(torch.float32, lse=lse)
     _call("ttt_hip_attn_forward", ctypes.byref(a), device=q.device)
 
 
 def attn_backward(q, k, v, out, dout, lse, delta, dq, dk, dv, scale):
     B, NH, S, D = q.shape
     sh = (B, NH, S, D)
-    _req(lse, "lse", torch.float32); _req(delta, "delta", torch.float32)
+    _req(torch.float32, lse=lse, delta=delta)
     a = _AttnBwd(_attn_tensor(q, "q", sh), _attn_tensor(k, "k", sh), _attn_tensor(v, "v", sh), _attn_tensor(out, "out", sh),
                  _attn_tensor(dout, "dout", sh), _attn_tensor(dq, "dq", sh), _attn_tensor(dk, "dk", sh), _attn_tensor(dv, "dv", sh),
                  lse.data_ptr(), delta.data_ptr(), B, NH, S, D, float(scale))
@@ -652,13 +615,11 @@ def attn_backward(q, k, v, out, dout, lse, delta, dq, dk, dv, scale):
 def attn_pre_forward(q_raw, k_raw, wq, bq, wk, bk, cos, sin, q, k, NH, n_text, eps):
     """Fused per-head LayerNorm(64) + RoPE of the attention's q and k; [B, S, NH*64] bf16 in and out."""
     B, S, D = q_raw.shape
-    for t, n in ((q_raw, "q_raw"), (k_raw, "k_raw"), (q, "q"), (k, "k")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((wq, "wq"), (bq, "bq"), (wk, "wk"), (bk, "bk"), (cos, "cos"), (sin, "sin")):
-        _req(t, n, torch.float32)
+    _req(torch.bfloat16, q_raw=q_raw, k_raw=k_raw, q=q, k=k)
+    _req(torch.float32, wq=wq, bq=bq, wk=wk, bk=bk, cos=cos, sin=sin)
     if D != NH * 64 or cos.shape[-1] != 64 or cos.shape[0] < S - n_text:
         raise RuntimeError("attn_pre_forward: head_dim must be 64 and the rope tables must cover the video tokens")
-    _call("ttt_hip_attn_pre_forward", B, S, NH, int(n_text), ctypes.c_float(eps), _p(q_raw), _p(k_raw), _p(wq), _p(bq), _p(wk), _p(bk),
+    _call("ttt_hip_attn_pre_forward", B, S, NH, int(n_text), eps, _p(q_raw), _p(k_raw), _p(wq), _p(bq), _p(wk), _p(bk),
           _p(cos), _p(sin), _p(q), _p(k), device=q_raw.device)
 
 
@@ -669,19 +630,13 @@ def attn_pre_partials(B, S, NH):
 def attn_pre_backward(q_raw, k_raw, dq, dk, wq, wk, cos, sin, dq_raw, dk_raw, part, NH, n_text, eps, ld_out=None):
     """``ld_out``: as in ``pre_backward`` (dq_raw / dk_raw as column blocks of one [B, S, 3 D] buffer whose third block is dV)."""
     B, S, D = q_raw.shape
-    for t, n in ((q_raw, "q_raw"), (k_raw, "k_raw")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((dq_raw, "dq_raw"), (dk_raw, "dk_raw")):
-        if ld_out is None:
-            _req(t, n, torch.bfloat16)
-        else:
-            _req_rows(t, n, (B, S, D), int(ld_out))
-    for t, n in ((wq, "wq"), (wk, "wk"), (cos, "cos"), (sin, "sin"), (part, "part")):
-        _req(t, n, torch.float32)
+    ld = None if ld_out is None else int(ld_out)
+    _req(torch.bfloat16, q_raw=q_raw, k_raw=k_raw)
+    _req_rows(ld, (B, S, D), dq_raw=dq_raw, dk_raw=dk_raw)
+    _req(torch.float32, wq=wq, wk=wk, cos=cos, sin=sin, part=part)
     tq, tk = _attn_tensor(dq, "dq", (B, NH, S, 64)), _attn_tensor(dk, "dk", (B, NH, S, 64))
-    _call("ttt_hip_attn_pre_backward_ld", B, S, NH, int(n_text), ctypes.c_float(eps), _p(q_raw), _p(k_raw), ctypes.byref(tq), ctypes.byref(tk),
-          _p(wq), _p(wk), _p(cos), _p(sin), _p(dq_raw), _p(dk_raw), ctypes.c_int64(D if ld_out is None else int(ld_out)), _p(part),
-          device=q_raw.device)
+    _call("ttt_hip_attn_pre_backward_ld", B, S, NH, int(n_text), eps, _p(q_raw), _p(k_raw), ctypes.byref(tq), ctypes.byref(tk),
+          _p(wq), _p(wk), _p(cos), _p(sin), _p(dq_raw), _p(dk_raw), D if ld is None else ld, _p(part), device=q_raw.device)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -689,14 +644,11 @@ def attn_pre_backward(q_raw, k_raw, dq, dk, wq, wk, cos, sin, dq_raw, dk_raw, pa
 def adaln_forward(vid, text, w, b, shift, scale1p, out, eps):
     B, Lv, D = vid.shape
     Lt = text.shape[1]
-    for t, n in ((vid, "vid"), (text, "text"), (out, "out")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((w, "w"), (b, "b"), (shift, "shift"), (scale1p, "scale1p")):
-        _req(t, n, torch.float32)
+    _req(torch.bfloat16, vid=vid, text=text, out=out)
+    _req(torch.float32, w=w, b=b, shift=shift, scale1p=scale1p)
     if tuple(out.shape) != (B, Lt + Lv, D) or tuple(shift.shape) != (B, 2, D) or tuple(scale1p.shape) != (B, 2, D):
         raise RuntimeError("adaln_forward: out must be [B, Lt+Lv, D], shift / scale1p [B, 2, D]")
-    _call("ttt_hip_adaln_forward", B, Lt, Lv, D, ctypes.c_float(eps), _p(vid), _p(text), _p(w), _p(b), _p(shift), _p(scale1p), _p(out),
-          device=vid.device)
+    _call("ttt_hip_adaln_forward", B, Lt, Lv, D, eps, _p(vid), _p(text), _p(w), _p(b), _p(shift), _p(scale1p), _p(out), device=vid.device)
 
 
 def adaln_backward_partials():
@@ -706,20 +658,17 @@ def adaln_backward_partials():
 def adaln_backward(vid, text, dout, w, b, scale1p, dvid, dtext, part, eps):
     B, Lv, D = vid.shape
     Lt = text.shape[1]
-    for t, n in ((vid, "vid"), (text, "text"), (dout, "dout"), (dvid, "dvid"), (dtext, "dtext")):
-        _req(t, n, torch.bfloat16)
-    for t, n in ((w, "w"), (b, "b"), (scale1p, "scale1p"), (part, "part")):
-        _req(t, n, torch.float32)
-    _call("ttt_hip_adaln_backward", B, Lt, Lv, D, ctypes.c_float(eps), _p(vid), _p(text), _p(dout), _p(w), _p(b), _p(scale1p),
+    _req(torch.bfloat16, vid=vid, text=text, dout=dout, dvid=dvid, dtext=dtext)
+    _req(torch.float32, w=w, b=b, scale1p=scale1p, part=part)
+    _call("ttt_hip_adaln_backward", B, Lt, Lv, D, eps, _p(vid), _p(text), _p(dout), _p(w), _p(b), _p(scale1p),
           _p(dvid), _p(dtext), _p(part), device=vid.device)
 
 
 def resgate_forward(vid, text, y, gate, ovid, otext):
     B, Lv, D = vid.shape
     Lt = text.shape[1]
-    for t, n in ((vid, "vid"), (text, "text"), (y, "y"), (ovid, "ovid"), (otext, "otext")):
-        _req(t, n, torch.bfloat16)
-    _req(gate, "gate", torch.float32)
+    _req(torch.bfloat16, vid=vid, text=text, y=y, ovid=ovid, otext=otext)
+    _req(torch.float32, gate=gate)
     if tuple(y.shape) != (B, Lt + Lv, D) or tuple(gate.shape) != (B, 2, D):
         raise RuntimeError("resgate_forward: y must be [B, Lt+Lv, D], gate [B, 2, D]")
     _call("ttt_hip_resgate_forward", B, Lt, Lv, D, _p(vid), _p(text), _p(y), _p(gate), _p(ovid), _p(otext), device=vid.device)
@@ -732,7 +681,6 @@ def resgate_backward_partials(D):
 def resgate_backward(dvid, dtext, y, gate, dy, dgate_part):
     B, Lv, D = dvid.shape
     Lt = dtext.shape[1]
-    for t, n in ((dvid, "dvid"), (dtext, "dtext"), (y, "y"), (dy, "dy")):
-        _req(t, n, torch.bfloat16)
-    _req(gate, "gate", torch.float32); _req(dgate_part, "dgate_part", torch.float32)
+    _req(torch.bfloat16, dvid=dvid, dtext=dtext, y=y, dy=dy)
+    _req(torch.float32, gate=gate, dgate_part=dgate_part)
     _call("ttt_hip_resgate_backward", B, Lt, Lv, D, _p(dvid), _p(dtext), _p(y), _p(gate), _p(dy), _p(dgate_part), device=dvid.device)

@@ -99,9 +99,10 @@ def _head_subset(NH):
 
 
 @pytest.mark.parametrize("B", [1, 2])
-@pytest.mark.parametrize("NH", [1, 8, 24, 48])
+@pytest.mark.parametrize("NH", [1, 3, 8, 24, 48])
 def test_pre_vs_oracle_heads_and_partials(NH, B):
-    """P = pre_backward_partials(NH) for the debug model (8), a tp = 2 shard of 5B (24) and 5B (48); 3 scenes, B = 2 time-reversed"""
+    """P = pre_backward_partials(NH) for the debug model (8), a tp = 2 shard of 5B (24) and 5B (48), one head, and an odd head count
+    (3: its thread period of 24 does not divide 2 048 x 256 threads, the persistent grid steps down); 3 scenes, B = 2 time-reversed"""
     e = ext()
     L, src, pos, rope = glue_maps(scene_meta(*META_3SC), reverse=B == 2)
     d = C.pre_case(B, L, NH, seed=NH + B)
@@ -237,18 +238,34 @@ def test_pre_and_post_ranges():
     check("post ranges", {"out": part.cpu()}, C.post_oracle(pc, src, 1e-6), {"out": (0, 1)})
 
 
-# ------------------------------------------------------------------------------------------------ post
-@pytest.mark.parametrize("NH", [2, 8, 20, 48, 64])
-def test_post_vs_oracle(NH):
-    """NH = 2 / 8 / 20 / 48 / 64: ln_team_waves 1 / 1 / 1 (a partial lane group) / 2 / 4; B = 2, L = 18 048, scene permutation;
-    rows of RMS 1e-3 .. 1 (eps matters).  Per-token operation: the oracle runs on chunks of scan positions."""
+def test_pre_forward_parts_odd_head_count():
+    """NH = 3 (24 threads per token: a block of 256 holds 10 2/3 tokens) in three t0 / tn parts cut at odd positions: bit-equal to
+    one call"""
     e = ext()
-    B, eps = 2, 1e-6
-    L, src, pos, rope = glue_maps(scene_meta(166, 3, 13, 30, 45))
-    assert L == 18048
-    pc = C.post_case(B, L, NH, seed=NH)
+    NH, B = 3, 2
+    L, src, pos, rope = glue_maps(scene_meta(*META_3SC), reverse=True)
+    d = C.pre_case(B, L, NH, seed=33)
+    q, k, v, w, b = (dev(d[n]) for n in ("q", "k", "v", "ln_w", "ln_b"))
+    rs, ss, ps = dev(rope), dev(src), dev(pos)
+    one, parts = ([nanbuf(B, NH, L, 64) for _ in range(3)] for _ in range(2))
+    e.pre_forward(q, k, v, rs, ss, ps, w, b, *one, NH)
+    cuts = [0, 1477, 2950, L]
+    for i in range(3):
+        e.pre_forward(q, k, v, rs, ss, ps, w, b, *parts, NH, t0=cuts[i], tn=cuts[i + 1] - cuts[i])
+    torch.cuda.synchronize()
+    for a, o in zip(parts, one):
+        assert not torch.isnan(o.float()).any() and torch.equal(a, o)
+
+
+# ------------------------------------------------------------------------------------------------ post
+def _post_vs_oracle(NH, B, L, src, seed):
+    e = ext()
+    eps = 1e-6
+    pc = C.post_case(B, L, NH, seed=seed)
     D = NH * 64
     Y, w, b, sd = dev(pc["Y"]), dev(pc["w"]), dev(pc["b"]), dev(src)
+    if src is None:
+        src = torch.arange(L)
     out = nanbuf(B, L, D)
     e.post_forward(Y, sd, w, b, out, eps)
     P = e.post_partials(B, L)
@@ -271,17 +288,30 @@ def test_post_vs_oracle(NH):
         mine["dY"].append(dY[:, :, ts]); theirs["dY"].append(r["dY"])
     got.update(out=torch.cat(mine["out"], 1), dY=torch.cat(mine["dY"], 2))
     want.update(out=torch.cat(theirs["out"], 1), dY=torch.cat(theirs["dY"], 2))
-    check(f"post NH={NH} P={P}", got, want, {"out": (0, 1), "dY": (0, 1, 2)}, psum=("dw", "db"))
+    check(f"post NH={NH} B={B} L={L} P={P}", got, want, {"out": (0, 1), "dY": (0, 1, 2)}, psum=("dw", "db"))
+
+
+@pytest.mark.parametrize("NH", [2, 8, 20, 48, 64])
+def test_post_vs_oracle(NH):
+    """NH = 2 / 8 / 20 / 48 / 64: ln_team_waves 1 / 1 / 1 (a partial lane group) / 2 / 4; B = 2, L = 18 048, scene permutation;
+    rows of RMS 1e-3 .. 1 (eps matters).  Per-token operation: the oracle runs on chunks of scan positions."""
+    L, src, pos, rope = glue_maps(scene_meta(166, 3, 13, 30, 45))
+    assert L == 18048
+    _post_vs_oracle(NH, 2, L, src, seed=NH)
+
+
+@pytest.mark.parametrize("NH,B,L,mapped", [(8, 1, 8256, True), (64, 2, 1100, True), (24, 2, 1100, False)])
+def test_post_vs_oracle_small(NH, B, L, mapped):
+    """Few tokens, where the token teams of the backward run ragged.  NH = 8, 8 256 tokens: one wave per team, eight teams, chunk
+    slot 0 alone active, 1 024 blocks x 8 tokens and a ragged second iteration.  NH = 64, 2 x 1 100: four waves per team, two teams,
+    chunk slot 2 wholly inactive, a ragged second iteration.  NH = 24 without a token map: all three chunk slots active."""
+    src = torch.randperm(L, generator=torch.Generator().manual_seed(L)).to(torch.int32) if mapped else None
+    _post_vs_oracle(NH, B, L, src, seed=NH + L)
 
 
 # ------------------------------------------------------------------------------------------------ gate
-@pytest.mark.parametrize("n_text", [0, 1, 498, 1506, 18048])
-@pytest.mark.parametrize("D", [512, 3072])
-def test_gate_vs_oracle(D, n_text):
-    """B = 2, L = 18 048; n_text = one scene's text at 3 s (498), three scenes at 9 s (1 506), none, one, all.  Per-feature
-    operation: the oracle runs on 256 features (the first and last octets among them) over every token."""
+def _gate_vs_oracle(D, n_text, B, L):
     e = ext()
-    B, L = 2, 18048
     gc = C.gate_case(B, L, D, seed=D + n_text)
     tt, tv = (torch.tanh(gc[n]).to(DEV) for n in ("at", "av"))
     res, y, g = (dev(gc[n]) for n in ("res", "y", "g"))
@@ -303,15 +333,26 @@ def test_gate_vs_oracle(D, n_text):
     if n_text >= L:
         assert not got["dtanh_v"].any()
         want["dtanh_v"] = got["dtanh_v"] = torch.ones(len(cols))
-    check(f"gate D={D} n_text={n_text} P={P}", got, want, {"out": (0, 1), "dy": (0, 1)}, psum=("dtanh_t", "dtanh_v"))
+    check(f"gate D={D} L={L} n_text={n_text} P={P}", got, want, {"out": (0, 1), "dy": (0, 1)}, psum=("dtanh_t", "dtanh_v"))
+
+
+@pytest.mark.parametrize("n_text", [0, 1, 498, 1506, 18048])
+@pytest.mark.parametrize("D", [512, 3072])
+def test_gate_vs_oracle(D, n_text):
+    """B = 2, L = 18 048; n_text = one scene's text at 3 s (498), three scenes at 9 s (1 506), none, one, all.  Per-feature
+    operation: the oracle runs on 256 features (the first and last octets among them) over every token."""
+    _gate_vs_oracle(D, n_text, 2, 18048)
+
+
+@pytest.mark.parametrize("n_text", [0, 498, 2100])
+def test_gate_vs_oracle_period_not_dividing_the_block(n_text):
+    """D = 520: the backward's thread period D / 8 = 65 does not divide 256, the persistent grid steps down to a multiple of 65 blocks
+    and a block's threads straddle rows of partials; B = 2, L = 2 100, no text / some / all"""
+    _gate_vs_oracle(520, n_text, 2, 2100)
 
 
 # ------------------------------------------------------------------------------------------------ AdaLN, residual gates
-@pytest.mark.parametrize("Lt,Lv", [(0, 3001), (1, 3001), (498, 3001), (498, 0)])
-@pytest.mark.parametrize("D", [512, 1280, 3072, 4096])
-def test_adaln_and_resgate_vs_oracle(D, Lt, Lv):
-    """D = 512 / 1280 / 3072 / 4096: ln_team_waves 1 (lanes e = 1, 2 idle) / 1 (a partial lane group) / 2 / 4; distinct
-    modulation per batch (B = 2); 3 001 video tokens: a ragged number of tokens per block of the backward (P = 256 per group)"""
+def _adaln_and_resgate_vs_oracle(D, Lt, Lv):
     e = ext()
     B, eps = 2, 1e-6
     ac = C.adaln_case(B, Lt, Lv, D, seed=D + Lt + Lv)
@@ -353,3 +394,20 @@ def test_adaln_and_resgate_vs_oracle(D, Lt, Lv):
         if not n:
             assert not got[k].any(), k
     check(f"resgate D={D} Lt={Lt} Lv={Lv} P={P}", got, want, rows, psum=[k for k, n in (("dg_t", Lt), ("dg_v", Lv)) if n])
+
+
+@pytest.mark.parametrize("Lt,Lv", [(0, 3001), (1, 3001), (498, 3001), (498, 0)])
+@pytest.mark.parametrize("D", [512, 1280, 3072, 4096])
+def test_adaln_and_resgate_vs_oracle(D, Lt, Lv):
+    """D = 512 / 1280 / 3072 / 4096: ln_team_waves 1 (lanes e = 1, 2 idle) / 1 (a partial lane group) / 2 / 4; distinct
+    modulation per batch (B = 2); 3 001 video tokens: a ragged number of tokens per block of the backward (P = 256 per group)"""
+    _adaln_and_resgate_vs_oracle(D, Lt, Lv)
+
+
+@pytest.mark.parametrize("D,Lt,Lv", [(512, 5, 2100), (4096, 3, 600), (520, 0, 2100), (520, 5, 2100), (520, 498, 0)])
+def test_adaln_and_resgate_vs_oracle_small(D, Lt, Lv):
+    """D = 512, 5 text tokens: fewer than the 256 blocks of their group, most of which never hold a valid token; 2 100 video tokens:
+    a ragged second iteration.  D = 4 096, 3 + 600 tokens: four waves per team, the team reduction [2, D] and the constants [3, D]
+    share the LDS area sized for 3 rows.  D = 520: the residual gate backward's thread period of 65 does not divide 256 (the
+    persistent grid steps down), with an empty text / video group."""
+    _adaln_and_resgate_vs_oracle(D, Lt, Lv)

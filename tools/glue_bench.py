@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""Timing of the token-wise glue kernels (AdaLN, post-norm, gated residual) at a CogVideoX-5B geometry: forward + backward of the
-autograd nodes the model uses, HIP events around each call (includes the small torch reductions of the partials), GB/s on the
-algorithmic bytes.  Run under `rocprofv3 --kernel-trace --stats` for the kernels alone.
+"""Timing of the token-wise glue kernels (TTT pre / post / gate, AdaLN, gated residual, the attention's q / k LayerNorm + RoPE) at a
+CogVideoX-5B geometry: forward + backward of the autograd nodes the model uses, HIP events around each call (includes the small
+torch reductions of the partials), GB/s on the algorithmic bytes.  Run under `rocprofv3 --kernel-trace --stats` for the kernels alone.
 
-    python tools/glue_bench.py [--video-length 9sec|3sec] [--iters 10]
+    python tools/glue_bench.py [--video-length 9sec|3sec] [--iters 10] [--library path/to/libttt_hip.so]
+
+`--library`: time another build of the kernels (the parent commit's, say) under this tree's Python, for an A/B in fresh processes.
 """
 import argparse
 import json
@@ -21,9 +23,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--video-length", default="9sec")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--library", default=None)
     a = ap.parse_args()
     import test_time_training as ext
-    from ttt_amd.models.ssm.fused import FusedAdaLN, FusedPost
+    from ttt_amd.models.cogvideo.attention import AttnPre
+    from ttt_amd.models.ssm.fused import FusedAdaLN, FusedGate, FusedPost, FusedPre, FusedResGate
+    if a.library:
+        ext._LIB_PATH = os.path.abspath(a.library)
     ext.load_library()
     dev = torch.device("cuda:0")
     Lt, Lv = {"3sec": (498, 17550), "9sec": (1506, 49950)}[a.video_length]
@@ -57,7 +63,40 @@ def main():
     o = FusedPost.apply(Y, w, b, src, 1e-6)
     timed("post_fwd", lambda: FusedPost.apply(Y, w, b, src, 1e-6), 2 * t2)
     timed("post_bwd", lambda: torch.autograd.grad(o, (Y, w, b), dout, retain_graph=True), 3 * t2)
-    print(json.dumps({"geometry": {"B": B, "Lt": Lt, "Lv": Lv, "D": D}, **res}))
+    del out, o
+    # TTT pre: q / k / v projections -> scan layout (3 reads, 3 writes; backward 6 reads, 3 writes)
+    qkv = [mk(B, L, D).requires_grad_(True) for _ in range(3)]
+    lnw, lnb = (torch.randn(NH, 64, device=dev, generator=g).requires_grad_(True) for _ in range(2))
+    rope = torch.randn(Lv, 32, 2, device=dev, generator=g)
+    pos = (torch.arange(L, device=dev) - Lt).clamp_min(-1).to(torch.int32)      # text tokens: no rotation
+    pos._ttt_max_pos = Lv
+    dX = [mk(B, NH, L, 64) for _ in range(3)]
+    outs = FusedPre.apply(*qkv, lnw, lnb, rope, src, pos, NH)
+    timed("pre_fwd", lambda: FusedPre.apply(*qkv, lnw, lnb, rope, src, pos, NH), 6 * t2)
+    timed("pre_bwd", lambda: torch.autograd.grad(outs, (*qkv, lnw, lnb), dX, retain_graph=True), 9 * t2)
+    del outs, dX
+    # gate of the TTT block and gated residuals of the transformer layer
+    alpha = [torch.randn(D, device=dev, generator=g).requires_grad_(True) for _ in range(2)]
+    y = mk(B, L, D).requires_grad_(True)
+    o = FusedGate.apply(qkv[0], y, *alpha, Lt)
+    timed("gate_fwd", lambda: FusedGate.apply(qkv[0], y, *alpha, Lt), 3 * t2)
+    timed("gate_bwd", lambda: torch.autograd.grad(o, (qkv[0], y, *alpha), dout, retain_graph=True), 3 * t2)
+    ov, ot = FusedResGate.apply(vid, text, y, mods[0], mods[1])
+    timed("resgate_fwd", lambda: FusedResGate.apply(vid, text, y, mods[0], mods[1]), 3 * t2)
+    timed("resgate_bwd", lambda: torch.autograd.grad((ov, ot), (vid, text, y, mods[0], mods[1]), (dout[:, Lt:], dout[:, :Lt]),
+                                                     retain_graph=True), 3 * t2)
+    del o, ov, ot, qkv
+    # attention q / k LayerNorm + RoPE on one 3-second segment
+    St, Sv = 498, 17550
+    S, a2 = St + Sv, 2 * B * (St + Sv) * D
+    qr, kr = (mk(B, S, D).requires_grad_(True) for _ in range(2))
+    nw = [torch.randn(64, device=dev, generator=g).requires_grad_(True) for _ in range(4)]
+    cos, sin = (torch.randn(Sv, 64, device=dev, generator=g) for _ in range(2))
+    dqk = [mk(B, S, NH, 64).transpose(1, 2) for _ in range(2)]
+    qk = AttnPre.apply(qr, kr, *nw, cos, sin, NH, St, 1e-6)
+    timed("attn_pre_fwd", lambda: AttnPre.apply(qr, kr, *nw, cos, sin, NH, St, 1e-6), 4 * a2)
+    timed("attn_pre_bwd", lambda: torch.autograd.grad(qk, (qr, kr, *nw), dqk, retain_graph=True), 6 * a2)
+    print(json.dumps({"geometry": {"B": B, "Lt": Lt, "Lv": Lv, "D": D, "attn_S": S}, "library": os.path.relpath(ext.library_path(), ROOT), **res}))
 
 
 if __name__ == "__main__":

@@ -12,44 +12,19 @@
 #include <stdint.h>
 #include "../../include/ttt_hip.h"
 #include "attn.h"
-#include "ttt_dpp.h"
+#include "glue_row.h"
 
 namespace ttt {
 namespace attn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void ld8(const __bf16* p, float (&o)[8]) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)a[j];
-}
-__device__ __forceinline__ void st8(__bf16* p, const float (&v)[8]) {
-    bf16x8 a;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = (__bf16)v[j];
-    *reinterpret_cast<bf16x8*>(p) = a;
-}
-__device__ __forceinline__ void ldf8(const float* p, float (&o)[8]) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-}
-__device__ __forceinline__ float rb(float x) { return (float)(__bf16)x; }
-
 // y = bf16(LN(x) * w + b); then, for video tokens, out = bf16(bf16(y*cos) + bf16(rot(y)*sin)), rot = (-y[2i+1], y[2i])
 __device__ __forceinline__ void ln_rope(const float (&x)[8], const float (&w)[8], const float (&b)[8], float eps,
                                         const float* cosr, const float* sinr, float (&out)[8], float (&xh)[8], float& rstd) {
-    float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j];
-    const float mean = sum8(s) * (1.0f / 64.0f);
-    float vs = 0.f;
+    for (int j = 0; j < 8; ++j) xh[j] = x[j];
+    rstd = 1.0f / sqrtf(centre_row(xh) * (1.0f / 64.0f) + eps);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { xh[j] = x[j] - mean; vs += xh[j] * xh[j]; }
-    rstd = 1.0f / sqrtf(sum8(vs) * (1.0f / 64.0f) + eps);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { xh[j] *= rstd; out[j] = rb(xh[j] * w[j] + b[j]); }
+    for (int j = 0; j < 8; ++j) { xh[j] *= rstd; out[j] = bf16_round(xh[j] * w[j] + b[j]); }
     if (cosr) {
         float c8[8], s8[8];
         ldf8(cosr, c8);
@@ -57,8 +32,8 @@ __device__ __forceinline__ void ln_rope(const float (&x)[8], const float (&w)[8]
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float a = out[2 * q], bb = out[2 * q + 1];
-            out[2 * q] = rb(rb(a * rb(c8[2 * q])) + rb(-bb * rb(s8[2 * q])));
-            out[2 * q + 1] = rb(rb(bb * rb(c8[2 * q + 1])) + rb(a * rb(s8[2 * q + 1])));
+            out[2 * q] = bf16_round(bf16_round(a * bf16_round(c8[2 * q])) + bf16_round(-bb * bf16_round(s8[2 * q])));
+            out[2 * q + 1] = bf16_round(bf16_round(bb * bf16_round(c8[2 * q + 1])) + bf16_round(a * bf16_round(s8[2 * q + 1])));
         }
     }
 }
@@ -93,18 +68,14 @@ __device__ __forceinline__ void ln_rope_bwd(const float (&x)[8], const float (&w
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float ga = g[2 * q], gb = g[2 * q + 1];
-            g[2 * q] = ga * rb(c8[2 * q]) + gb * rb(s8[2 * q + 1]);
-            g[2 * q + 1] = gb * rb(c8[2 * q + 1]) - ga * rb(s8[2 * q]);
+            g[2 * q] = ga * bf16_round(c8[2 * q]) + gb * bf16_round(s8[2 * q + 1]);
+            g[2 * q + 1] = gb * bf16_round(c8[2 * q + 1]) - ga * bf16_round(s8[2 * q]);
         }
     }
-    float s = 0.f;
+    float xh[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s += x[j];
-    const float mean = sum8(s) * (1.0f / 64.0f);
-    float vs = 0.f, xh[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { xh[j] = x[j] - mean; vs += xh[j] * xh[j]; }
-    const float rstd = 1.0f / sqrtf(sum8(vs) * (1.0f / 64.0f) + eps);
+    for (int j = 0; j < 8; ++j) xh[j] = x[j];
+    const float rstd = 1.0f / sqrtf(centre_row(xh) * (1.0f / 64.0f) + eps);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {

@@ -149,7 +149,7 @@ static OverlapRes* overlap_resources() {
 // Revision 4 (round 3): the same chunk walk and the same two-stream schedule over the slim step record:
 //   A  s4::launch_recompute4   (ttt_mfma_rc4.hip: 8-wave recompute, 120.5 KiB per step)
 //   B  s4::launch_sweep_cluster4 (ttt_mfma_bwd4.hip: cluster sweep with deriver waves)
-//   C  s4::launch_tail4        (dK / dQ; beside the next chunk's sweep)
+//   C  s4::launch_tail5        (dK / dQ; beside the next chunk's sweep)
 static int mlp_backward4(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, hipStream_t s, int per_launch, unsigned* err_word) {
     const int nbh = d->B * d->NH, G = d->G, NC = d->NC;
     const int K = (NC + G - 1) / G;

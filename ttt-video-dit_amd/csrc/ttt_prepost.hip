@@ -14,41 +14,10 @@
 #include <stdint.h>
 #include "../../include/ttt_hip.h"
 #include "ttt_prepost.h"
-#include "ttt_dpp.h"
+#include "glue_row.h"
 
 namespace ttt {
 namespace prepost {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void ld8(const __bf16* p, float (&o)[8]) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)a[j];
-}
-__device__ __forceinline__ bf16x8 ld8_raw(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ bf16x8 zero8_raw() {
-    bf16x8 z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.0f;
-    return z;
-}
-__device__ __forceinline__ void cvt8(const bf16x8& a, float (&o)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)a[j];
-}
-__device__ __forceinline__ void st8(__bf16* p, const float (&v)[8]) {
-    bf16x8 a;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = (__bf16)v[j];
-    *reinterpret_cast<bf16x8*>(p) = a;
-}
-__device__ __forceinline__ void ldf8(const float* p, float (&o)[8]) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-    o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-}
-__device__ __forceinline__ float bf16_round(float x) { return (float)(__bf16)x; }
 
 constexpr float NORM_EPS = 1e-12f;   // F.normalize default (ttt_layer.py:264-266)
 constexpr float TGT_EPS = 1e-8f;     // ln_reconstruction_target (ttt_layer.py:229)
@@ -100,14 +69,10 @@ __global__ __launch_bounds__(256) void pre_fwd_kernel(PreArgs a) {
         norm_rope(k, cs, y, inv);
         st8(a.XK + out_off, y);
         // V <- gamma_h * LN_unbiased(V - K) + beta_h + K      (K = the bf16 value just stored)
-        float d[8], s = 0.f;
+        float d[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { d[j] = v[j] - y[j]; s += d[j]; }
-        const float mean = sum8(s) * (1.0f / 64.0f);
-        float vs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { d[j] -= mean; vs += d[j] * d[j]; }
-        const float inv_s = 1.0f / (sqrtf(sum8(vs) * (1.0f / 63.0f)) + TGT_EPS);
+        for (int j = 0; j < 8; ++j) d[j] = v[j] - y[j];
+        const float inv_s = 1.0f / (sqrtf(centre_row(d) * (1.0f / 63.0f)) + TGT_EPS);
         float g[8], be[8];
         ldf8(a.ln_w + h * 64 + 8 * o, g);
         ldf8(a.ln_b + h * 64 + 8 * o, be);
@@ -172,14 +137,10 @@ __global__ __launch_bounds__(256) void pre_bwd_kernel(PreBwdArgs a) {
         ld8(a.dXV + out_off, gv);
         // ---- V path: vout = gamma * dn + beta + kb, dn = (d - mean) / (std + eps), d = v - kb
         norm_rope(k, cs, kb, inv);
-        float d[8], s = 0.f;
+        float d[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { d[j] = v[j] - kb[j]; s += d[j]; }
-        const float mean = sum8(s) * (1.0f / 64.0f);
-        float vs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { d[j] -= mean; vs += d[j] * d[j]; }
-        const float sd = sqrtf(sum8(vs) * (1.0f / 63.0f));
+        for (int j = 0; j < 8; ++j) d[j] = v[j] - kb[j];
+        const float sd = sqrtf(centre_row(d) * (1.0f / 63.0f));
         const float inv_s = 1.0f / (sd + TGT_EPS);
         float s1 = 0.f, s2 = 0.f, ddn[8];
 #pragma unroll
@@ -228,6 +189,18 @@ __device__ __forceinline__ float block_sum(float v, float* sh, int nw) {
     float t = 0.f;
     for (int i = 0; i < nw; ++i) t += sh[i];
     return t;
+}
+// LayerNorm statistics of a D-feature row spread over the block, 8 features per thread (an inactive thread holds zeros and
+// contributes none): centres x in place and returns 1 / sqrt(var + eps), var biased
+__device__ __forceinline__ float block_centre_rstd(float (&x)[8], bool act, int D, float eps, float* sh, int nw) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += x[j];
+    const float mean = block_sum(s, sh, nw) / D;
+    float vs = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { x[j] = act ? x[j] - mean : 0.f; vs += x[j] * x[j]; }
+    return 1.0f / sqrtf(block_sum(vs, sh, nw) / D + eps);
 }
 
 // ---- LayerNorm-over-D backward kernels: token teams ----------------------------------------------------------------------
@@ -326,14 +299,7 @@ __global__ void post_fwd_kernel(PostArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) y[j] = 0.f;
         if (act) ld8(a.Y + (((size_t)b * a.NH + h) * a.L + tp) * 64 + 8 * o, y);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += y[j];
-        const float mean = block_sum(s, sh, nw) / D;
-        float vs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { y[j] = act ? y[j] - mean : 0.f; vs += y[j] * y[j]; }
-        const float rstd = 1.0f / sqrtf(block_sum(vs, sh, nw) / D + a.eps);
+        const float rstd = block_centre_rstd(y, act, D, a.eps, sh, nw);
 #pragma unroll
         for (int j = 0; j < 8; ++j) y[j] = y[j] * rstd * w8[j] + b8[j];
         if (act) st8(a.out + ((size_t)b * a.L + src) * D + h * 64 + 8 * o, y);
@@ -520,14 +486,7 @@ __global__ void adaln_fwd_kernel(AdaLNArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = 0.f;
         if (act) ld8(src + o8, x);
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s += x[j];
-        const float mean = block_sum(s, sh, nw) / D;
-        float vs = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { x[j] = act ? x[j] - mean : 0.f; vs += x[j] * x[j]; }
-        const float rstd = 1.0f / sqrtf(block_sum(vs, sh, nw) / D + a.eps);
+        const float rstd = block_centre_rstd(x, act, D, a.eps, sh, nw);
         if (act) {
             ldf8(a.shift + ((size_t)b * 2 + g) * D + o8, sf);
             ldf8(a.scale1p + ((size_t)b * 2 + g) * D + o8, sc);
@@ -728,17 +687,19 @@ void pre_forward(const PreArgs& a, hipStream_t s) {
     const long total = (long)a.B * (a.tn ? a.tn : a.L) * a.NH * 8;
     hipLaunchKernelGGL(pre_fwd_kernel, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, s, a);
 }
-int pre_backward_partials(int NH) {          // P for a launch of pre_backward
-    const int per = NH * 8;                  // threads per (head, octet) period
+// The persistent backward kernels (pre, gate, residual gate): the largest grid of at most 2048 blocks of 256 threads whose thread
+// count is a multiple of `period`, so that a thread keeps its feature octet over its grid-stride loop.  Every `period` threads
+// write one row of partial sums: the launchers and the *_partials functions the callers size their buffers with both come here.
+static int persistent_blocks(int period) {
     int blocks = 2048;
-    while ((long)blocks * 256 % per) --blocks;
-    return (int)((long)blocks * 256 / per);
+    while ((long)blocks * 256 % period) --blocks;
+    return blocks;
 }
+static int persistent_partials(int period) { return (int)((long)persistent_blocks(period) * 256 / period); }
+
+int pre_backward_partials(int NH) { return persistent_partials(NH * 8); }      // (period: the (head, octet) pairs of a token)
 void pre_backward(const PreBwdArgs& a, hipStream_t s) {
-    const int per = a.NH * 8;
-    int blocks = 2048;
-    while ((long)blocks * 256 % per) --blocks;
-    hipLaunchKernelGGL(pre_bwd_kernel, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(pre_bwd_kernel, dim3(persistent_blocks(a.NH * 8)), dim3(256), 0, s, a);
 }
 int post_blocks(int B, int L) {
     const long n = (long)B * L;
@@ -757,19 +718,10 @@ void gate_forward(const GateArgs& a, hipStream_t s) {
     const long total = (long)a.B * a.L * (a.D / 8);
     hipLaunchKernelGGL(gate_fwd_kernel, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, s, a);
 }
-int gate_backward_partials(int D) {
-    const int per = D / 8;
-    int blocks = 2048;
-    while ((long)blocks * 256 % per) --blocks;
-    return (int)((long)blocks * 256 / per);
-}
+int gate_backward_partials(int D) { return persistent_partials(D / 8); }
 void gate_backward(const GateBwdArgs& a, hipStream_t s) {
-    const int per = a.D / 8;
-    int blocks = 2048;
-    while ((long)blocks * 256 % per) --blocks;
-    hipLaunchKernelGGL(gate_bwd_kernel, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gate_bwd_kernel, dim3(persistent_blocks(a.D / 8)), dim3(256), 0, s, a);
 }
-
 
 int adaln_blocks(int B, int Lt, int Lv) {
     const long n = (long)B * (Lt + Lv);
@@ -790,12 +742,9 @@ void resgate_forward(const ResGateArgs& a, hipStream_t s) {
     const long total = (long)a.B * (a.Lt + a.Lv) * (a.D / 8);
     hipLaunchKernelGGL(resgate_fwd_kernel, dim3(grid_for(total, 256, 256 * 32)), dim3(256), 0, s, a);
 }
-int resgate_backward_partials(int D) { return gate_backward_partials(D); }
+int resgate_backward_partials(int D) { return persistent_partials(D / 8); }
 void resgate_backward(const ResGateBwdArgs& a, hipStream_t s) {
-    const int per = a.D / 8;
-    int blocks = 2048;
-    while ((long)blocks * 256 % per) --blocks;
-    hipLaunchKernelGGL(resgate_bwd_kernel, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(resgate_bwd_kernel, dim3(persistent_blocks(a.D / 8)), dim3(256), 0, s, a);
 }
 
 }  // namespace prepost

@@ -23,6 +23,18 @@ def fused_available(x: torch.Tensor, head_dim: int) -> bool:
     return x.is_cuda and x.dtype == _BF16 and head_dim == 64
 
 
+def _f32(t):
+    """A parameter / modulation tensor as the kernels read it: fp32, contiguous, outside the graph."""
+    return t.detach().to(_F32).contiguous()
+
+
+def _summed(P, shape, device, launch, n=1):
+    """``launch(*parts)`` on ``n`` fp32 ``[P, *shape]`` buffers (a backward kernel's partial sums, ``P`` its ``*_partials``) -> the sums over P"""
+    parts = [torch.empty(P, *shape, device=device, dtype=_F32) for _ in range(n)]
+    launch(*parts)
+    return [p.sum(0) for p in parts]
+
+
 def qkv_grad_blocks(like: torch.Tensor):
     """Three ``[B, L, D]`` gradient tensors (d q_raw, d k_raw, d v_raw of projections that read the SAME input) as the column blocks
     of ONE ``[B, L, 3 D]`` buffer: ``Linear3.backward`` (``ttt_amd/infra/fused_linear.py``) recognises the layout and forms the
@@ -34,6 +46,14 @@ def qkv_grad_blocks(like: torch.Tensor):
     return buf[..., :D], buf[..., D:2 * D], buf[..., 2 * D:]
 
 
+def _pre_backward(ext, q, k, v, rope, src, pos, w32, dXQ, dXK, dXV, NH):
+    """Backward of the pre kernel -> d q_raw, d k_raw, d v_raw (``qkv_grad_blocks``) and fp32 d ln_w, d ln_b ``[NH, 64]``."""
+    dq, dk, dv = qkv_grad_blocks(q)
+    launch = lambda pw, pb: ext.pre_backward(q, k, v, rope, src, pos, w32, dXQ, dXK, dXV, dq, dk, dv, pw, pb, NH, ld_out=dq.stride(1))
+    dw, db = _summed(ext.pre_backward_partials(NH), q.shape[-1:], q.device, launch, 2)
+    return dq, dk, dv, dw.view(NH, -1), db.view(NH, -1)
+
+
 class FusedPre(torch.autograd.Function):
     """(XQ_raw, XK_raw, XV_raw [B,L,NH*64], ln_w, ln_b [NH,64], rope [n,32,2] | None, src, pos [L] int32 | None)
     -> XQ, XK, XV [B,NH,L,64] in scan order (token permutation, L2-norm, RoPE, LayerNorm target fused)."""
@@ -43,7 +63,7 @@ class FusedPre(torch.autograd.Function):
         ext = _ext()
         B, L, D = XQ_raw.shape
         q, k, v = XQ_raw.contiguous(), XK_raw.contiguous(), XV_raw.contiguous()
-        w32, b32 = ln_w.detach().to(_F32).contiguous(), ln_b.detach().to(_F32).contiguous()
+        w32, b32 = _f32(ln_w), _f32(ln_b)
         outs = [torch.empty(B, NH, L, D // NH, device=q.device, dtype=_BF16) for _ in range(3)]
         ext.pre_forward(q, k, v, rope, src, pos, w32, b32, *outs, NH, n_pos=getattr(pos, "_ttt_max_pos", None))
         ctx.save_for_backward(q, k, v, w32, rope, src, pos)
@@ -54,16 +74,8 @@ class FusedPre(torch.autograd.Function):
     def backward(ctx, dXQ, dXK, dXV):
         ext = _ext()
         q, k, v, w32, rope, src, pos = ctx.saved_tensors
-        NH = ctx.NH
-        P = ext.pre_backward_partials(NH)
-        dq, dk, dv = qkv_grad_blocks(q)
-        pw = torch.empty(P, q.shape[-1], device=q.device, dtype=_F32)
-        pb = torch.empty_like(pw)
-        ext.pre_backward(q, k, v, rope, src, pos, w32, dXQ.contiguous(), dXK.contiguous(), dXV.contiguous(), dq, dk, dv, pw, pb, NH,
-                         ld_out=dq.stride(1))
-        dw = pw.sum(0).view(NH, -1).to(ctx.param_dtype)
-        db = pb.sum(0).view(NH, -1).to(ctx.param_dtype)
-        return dq, dk, dv, dw, db, None, None, None, None
+        dq, dk, dv, dw, db = _pre_backward(ext, q, k, v, rope, src, pos, w32, dXQ.contiguous(), dXK.contiguous(), dXV.contiguous(), ctx.NH)
+        return dq, dk, dv, dw.to(ctx.param_dtype), db.to(ctx.param_dtype), None, None, None, None
 
 
 class FusedPost(torch.autograd.Function):
@@ -74,7 +86,7 @@ class FusedPost(torch.autograd.Function):
         ext = _ext()
         B, NH, L, F = Y.shape
         y = Y.contiguous()
-        w32, b32 = weight.detach().to(_F32).contiguous(), bias.detach().to(_F32).contiguous()
+        w32, b32 = _f32(weight), _f32(bias)
         from ttt_amd.models.ssm.pipeline import injected
         out = injected("post")
         if out is None:
@@ -89,12 +101,9 @@ class FusedPost(torch.autograd.Function):
         ext = _ext()
         y, w32, src = ctx.saved_tensors
         B, NH, L, F = y.shape
-        P = ext.post_partials(B, L)
-        dY = torch.empty_like(y)
-        pw = torch.empty(P, NH * F, device=y.device, dtype=_F32)
-        pb = torch.empty_like(pw)
-        ext.post_backward(y, g.contiguous(), src, w32, dY, pw, pb, ctx.eps)
-        return dY, pw.sum(0).to(ctx.param_dtype), pb.sum(0).to(ctx.param_dtype), None, None
+        dY, g = torch.empty_like(y), g.contiguous()
+        dw, db = _summed(ext.post_partials(B, L), w32.shape, y.device, lambda pw, pb: ext.post_backward(y, g, src, w32, dY, pw, pb, ctx.eps), 2)
+        return dY, dw.to(ctx.param_dtype), db.to(ctx.param_dtype), None, None
 
 
 class FusedGate(torch.autograd.Function):
@@ -104,7 +113,7 @@ class FusedGate(torch.autograd.Function):
     def forward(ctx, res, y, alpha_text, alpha_video, n_text):
         ext = _ext()
         r, yy = res.contiguous(), y.contiguous()
-        tt, tv = torch.tanh(alpha_text.detach().to(_F32)).contiguous(), torch.tanh(alpha_video.detach().to(_F32)).contiguous()
+        tt, tv = torch.tanh(_f32(alpha_text)), torch.tanh(_f32(alpha_video))
         out = torch.empty_like(r)
         ext.gate_forward(r, yy, tt, tv, out, n_text)
         ctx.save_for_backward(yy, tt, tv)
@@ -116,13 +125,9 @@ class FusedGate(torch.autograd.Function):
         ext = _ext()
         yy, tt, tv = ctx.saved_tensors
         g = g.contiguous()
-        D = g.shape[-1]
-        P = ext.gate_backward_partials(D)
-        dy = torch.empty_like(g)
-        part = torch.empty(P, 2, D, device=g.device, dtype=_F32)
-        ext.gate_backward(g, yy, tt, tv, dy, part, ctx.n_text)
-        dt = part.sum(0)                                   # d/d tanh(alpha)
-        da_t = (dt[0] * (1 - tt * tt)).to(ctx.param_dtype)
+        dy, D = torch.empty_like(g), g.shape[-1]
+        dt, = _summed(ext.gate_backward_partials(D), (2, D), g.device, lambda part: ext.gate_backward(g, yy, tt, tv, dy, part, ctx.n_text))
+        da_t = (dt[0] * (1 - tt * tt)).to(ctx.param_dtype)       # (dt: d/d tanh(alpha))
         da_v = (dt[1] * (1 - tv * tv)).to(ctx.param_dtype)
         return g, dy, da_t, da_v, None
 
@@ -143,7 +148,7 @@ class FusedPreScanMLP(torch.autograd.Function):
         B, L, D = XQ_raw.shape
         Fh = D // NH
         q, k, v = XQ_raw.contiguous(), XK_raw.contiguous(), XV_raw.contiguous()
-        w32, b32 = ln_w.detach().to(_F32).contiguous(), ln_b.detach().to(_F32).contiguous()
+        w32, b32 = _f32(ln_w), _f32(ln_b)
         CS = eta.shape[-1]
         NC = L // CS
         K = math.ceil(NC / G)
@@ -206,14 +211,10 @@ class FusedPreScanMLP(torch.autograd.Function):
                          d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
         del XQ, XK, XV
         # pre backward (re-uses the raw projections)
-        P = ext.pre_backward_partials(NH)
-        dq, dk, dv = qkv_grad_blocks(q)
-        pw = torch.empty(P, D, device=dev, dtype=_F32)
-        pb = torch.empty_like(pw)
         flat = lambda t: t.view(B, NH, L, Fh)
-        ext.pre_backward(q, k, v, rope, src, pos, w32, flat(dQ), flat(dK), flat(dV), dq, dk, dv, pw, pb, NH, ld_out=dq.stride(1))
-        g_w = (pw.sum(0).view(NH, Fh) + d_lnw.sum(dim=0).squeeze(1)).to(ln_dt)
-        g_b = (pb.sum(0).view(NH, Fh) + d_lnb.sum(dim=0).squeeze(1)).to(ln_dt)
+        dq, dk, dv, dw, db = _pre_backward(ext, q, k, v, rope, src, pos, w32, flat(dQ), flat(dK), flat(dV), NH)
+        g_w = (dw + d_lnw.sum(dim=0).squeeze(1)).to(ln_dt)
+        g_b = (db + d_lnb.sum(dim=0).squeeze(1)).to(ln_dt)
         row = d_eta.transpose(-2, -1)
         rows = eta_shape[-2]
         d_eta_full = row if rows == 1 else torch.nn.functional.pad(row, (0, 0, rows - 1, 0))
@@ -231,10 +232,10 @@ class FusedAdaLN(torch.autograd.Function):
         ext = _ext()
         v, t = vid.contiguous(), text.contiguous()
         B, Lv, D = v.shape
-        w32, b32 = w.detach().to(_F32).contiguous(), b.detach().to(_F32).contiguous()
+        w32, b32 = _f32(w), _f32(b)
         # [B, 2, D], group 0 = text, 1 = video; "1 + scale" is formed in the activation dtype like the unfused modulate
-        shift = torch.stack((shift_t, shift_v), dim=1).detach().to(_F32).contiguous()
-        scale1p = torch.stack((1 + scale_t, 1 + scale_v), dim=1).detach().to(_F32).contiguous()
+        shift = _f32(torch.stack((shift_t, shift_v), dim=1))
+        scale1p = _f32(torch.stack((1 + scale_t, 1 + scale_v), dim=1))
         out = torch.empty(B, t.shape[1] + Lv, D, device=v.device, dtype=_BF16)
         ext.adaln_forward(v, t, w32, b32, shift, scale1p, out, float(eps))
         ctx.save_for_backward(v, t, w32, b32, scale1p)
@@ -267,7 +268,7 @@ class FusedResGate(torch.autograd.Function):
     def forward(ctx, vid, text, y, gate_v, gate_t):
         ext = _ext()
         v, t, yy = vid.contiguous(), text.contiguous(), y.contiguous()
-        gate = torch.stack((gate_t, gate_v), dim=1).detach().to(_F32).contiguous()
+        gate = _f32(torch.stack((gate_t, gate_v), dim=1))
         ov, ot = torch.empty_like(v), torch.empty_like(t)
         ext.resgate_forward(v, t, yy, gate, ov, ot)
         ctx.save_for_backward(yy, gate)
@@ -280,9 +281,7 @@ class FusedResGate(torch.autograd.Function):
         yy, gate = ctx.saved_tensors
         dv, dt = dv.contiguous(), dt.contiguous()
         B, L, D = yy.shape
-        P = ext.resgate_backward_partials(D)
         dy = torch.empty_like(yy)
-        part = torch.empty(P, B, 2, D, device=yy.device, dtype=_F32)
-        ext.resgate_backward(dv, dt, yy, gate, dy, part)
-        dg = part.sum(0).to(ctx.gdt)                               # [B, 2, D]
+        dg, = _summed(ext.resgate_backward_partials(D), (B, 2, D), yy.device, lambda part: ext.resgate_backward(dv, dt, yy, gate, dy, part))
+        dg = dg.to(ctx.gdt)                                        # [B, 2, D]
         return dv, dt, dy, dg[:, 1], dg[:, 0]

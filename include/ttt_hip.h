@@ -51,13 +51,17 @@ extern "C" {
  *    second CU runs the output path from them: same bits, -25 % per scan) - and ttt_hip_mlp_forward_chunk USES its workspace arguments
  *    (NULL / too small: the one-workgroup scan, as ABI 4 callers get it).  A pair whose second workgroup is never scheduled gives up
  *    after 2 s, poisons its outputs with NaN and sets the sticky error that ttt_hip_sweep_error_clear() acknowledges (return code -3
- *    of the next call), like the backward's cluster.  Signatures unchanged. */
+ *    of the next call), like the backward's cluster.  Signatures unchanged.
+ *    (Still 5: TTT-Linear at CS=64 gained MFMA kernels that run on an explicit TTT_IMPL_MFMA only - a request that used to be refused
+ *    with -1; what TTT_IMPL_AUTO resolves to, every signature and every tensor contract are unchanged.) */
 #define TTT_HIP_ABI_VERSION 5
 
 enum { TTT_DTYPE_BF16 = 0, TTT_DTYPE_F32 = 1 };
 /* implementation selector: AUTO picks the MFMA kernels when the geometry is supported - bf16, F=64 and
  * TTT-MLP forward/backward at CS=64, TTT-MLP forward at CS=16, TTT-Linear forward/backward at CS=16 -
- * and the generic fp32-arithmetic kernels otherwise; TTT_IMPL_MFMA makes an unsupported geometry an error. */
+ * and the generic fp32-arithmetic kernels otherwise; TTT_IMPL_MFMA makes an unsupported geometry an error.
+ * TTT-Linear forward/backward at CS=64 on explicit TTT_IMPL_MFMA: the MFMA kernels of that geometry are opt-in, AUTO keeps
+ * resolving it to the generic kernels. */
 enum { TTT_IMPL_AUTO = 0, TTT_IMPL_GENERIC = 1, TTT_IMPL_MFMA = 2 };
 
 typedef struct ttt_dims {

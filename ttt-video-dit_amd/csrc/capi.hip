@@ -30,7 +30,8 @@ static int check_dims(const ttt_dims* d) {
 static int resolve(const ttt_dims* d, bool mlp, bool bwd) {
     if (d->impl == TTT_IMPL_GENERIC) return ttt::generic::supports(d) ? TTT_IMPL_GENERIC : -1;
     if (d->impl == TTT_IMPL_MFMA) return ttt::mfma::supports(d, mlp, bwd) ? TTT_IMPL_MFMA : -1;
-    if (ttt::mfma::supports(d, mlp, bwd)) return TTT_IMPL_MFMA;
+    // TTT-Linear at CS = 64: the MFMA kernels are opt-in (explicit TTT_IMPL_MFMA above); AUTO stays on the generic kernels
+    if (ttt::mfma::supports(d, mlp, bwd) && (mlp || d->CS != 64)) return TTT_IMPL_MFMA;
     if (ttt::generic::supports(d)) return TTT_IMPL_GENERIC;
     return -1;
 }

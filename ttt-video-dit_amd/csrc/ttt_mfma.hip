@@ -2,7 +2,7 @@
 //   TTT-MLP forward   CS = 64: ttt_mfma2.hip (8-wave register-resident scan)   CS = 16: ttt_mfma16.hip
 //   TTT-MLP backward  CS = 64: revision 4 - ttt_mfma_rc4.hip (group recompute), ttt_mfma_bwd4.hip (cluster sweep with deriver
 //                     waves, tail), orchestrated by ttt_mfma_bwd2.hip
-//   TTT-Linear forward / backward at CS = 16: ttt_mfma16.hip
+//   TTT-Linear forward / backward at CS = 16: ttt_mfma16.hip ; at CS = 64 (explicit TTT_IMPL_MFMA only): ttt_lin64_body.h, same file
 // (Round 1's 4-wave scan / recompute kernel lived here; its last user, revision 3 of the backward, lost its round-3 A/B against
 // revision 4 - 17.8 vs 13.4 ms per backward at NC = 804, profiles/r3h_* - and was removed with it.)
 #include "ttt_mfma.h"
@@ -20,7 +20,7 @@ unsigned long long* get_debug_timing() { return g_dbg; }
 bool supports(const ttt_dims* d, bool mlp, bool backward) {
     if (!(d->F == 64 && d->act_dtype == TTT_DTYPE_BF16)) return false;
     if (d->CS == 16) return !backward || !mlp;  // mini-batches of 16 (ttt_mfma16.hip): MLP forward, Linear forward + backward
-    if (!mlp) return false;
+    if (!mlp) return d->CS == 64;                // TTT-Linear at 64 (ttt_lin64_body.h); capi.hip keeps AUTO on the generic kernels
     return d->CS == 64 && (!backward || bwd_available());
 }
 
@@ -63,7 +63,8 @@ void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipS
     p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints;
     p.out = (__bf16*)a->XQW;
     p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    launch_linear_forward_cs16(p, d->B * d->NH, s);
+    if (d->CS == 16) launch_linear_forward_cs16(p, d->B * d->NH, s);
+    else launch_linear_forward_cs64(p, d->B * d->NH, s);
 }
 void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hipStream_t s) {
     wv::Lin16Params p = {};
@@ -77,7 +78,8 @@ void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hip
     p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init;
     p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
     p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    launch_linear_backward_cs16(p, d->B * d->NH, s);
+    if (d->CS == 16) launch_linear_backward_cs16(p, d->B * d->NH, s);
+    else launch_linear_backward_cs64(p, d->B * d->NH, s);
 }
 
 }  // namespace mfma

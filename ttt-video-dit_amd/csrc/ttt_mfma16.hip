@@ -38,6 +38,7 @@
 #include "ttt_mfma_int.h"
 #define TTT_WV_FN __device__ __forceinline__
 #include "ttt_lin16_body.h"
+#include "ttt_lin64_body.h"
 #include "ttt_mlp16_body.h"
 #include "once_per_device.h"
 
@@ -158,6 +159,19 @@ __global__ __launch_bounds__(64) void linear_bwd16_kernel(wv::Lin16Params p) {
     lin16::backward(bk, p, blockIdx.x);
 }
 
+// TTT-Linear at mini-batches of 64 tokens (ttt_lin64_body.h): one workgroup of four waves per (b, h), one wave per SIMD - up to 512
+// registers per lane.  Runs on an explicit TTT_IMPL_MFMA only (capi.hip: resolve()).
+__global__ __launch_bounds__(64 * lin64::WAVES) void linear_fwd_cs64_kernel(wv::Lin16Params p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin64::forward(bk, p, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * lin64::WAVES) void linear_bwd_cs64_kernel(wv::Lin16Params p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin64::backward(bk, p, blockIdx.x);
+}
+
 }  // namespace v16
 
 static void lin_attr_once() {
@@ -175,6 +189,22 @@ void launch_linear_forward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t 
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
     lin_attr_once();
     hipLaunchKernelGGL(v16::linear_bwd16_kernel, dim3(n_bh), dim3(64), lin16::WAVE_LDS_BWD, s, p);
+}
+
+static void lin64_attr_once() {
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::linear_fwd_cs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::GROUP_LDS);
+        (void)hipFuncSetAttribute((const void*)v16::linear_bwd_cs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::GROUP_LDS_BWD);
+    });
+}
+void launch_linear_forward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
+    lin64_attr_once();
+    hipLaunchKernelGGL(v16::linear_fwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS, s, p);
+}
+void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
+    lin64_attr_once();
+    hipLaunchKernelGGL(v16::linear_bwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS_BWD, s, p);
 }
 
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*, hipStream_t s) {

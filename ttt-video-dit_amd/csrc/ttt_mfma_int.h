@@ -48,6 +48,8 @@ int get_debug_fast_records();
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long* dbg, hipStream_t s);
 void launch_linear_forward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h)
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
+void launch_linear_forward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h)
+void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void set_debug_dump(float* buf);
 unsigned long long* get_debug_timing();
 void set_debug_overlap_tail(int v);   // backward schedule: 0 one stream, 1 tail of chunk c beside the sweep of chunk c-1, 2 (default) the next recompute too

@@ -290,7 +290,16 @@ def _check5(XQ) -> None:
         raise RuntimeError("XQ: expected a 5-D tensor [B, NH, NC, CS, F]")
 
 
-def _dims(B, NH, NC, CS, F, G, act_dtype) -> _Dims:
+def _impl_code(impl) -> int:
+    """selector of one call: None = the global one (``set_impl``), or 'auto' / 'generic' / 'mfma'"""
+    if impl is None:
+        return _state["impl"]
+    if impl not in _IMPL_NAMES:
+        raise ValueError(f"impl: expected None, 'auto', 'generic' or 'mfma', got {impl!r}")
+    return _IMPL_NAMES[impl]
+
+
+def _dims(B, NH, NC, CS, F, G, act_dtype, impl=None) -> _Dims:
     if act_dtype == torch.bfloat16:
         code = 0
     elif act_dtype == torch.float32:
@@ -299,7 +308,7 @@ def _dims(B, NH, NC, CS, F, G, act_dtype) -> _Dims:
         raise RuntimeError(f"activations must be bfloat16 or float32, got {act_dtype}")
     if G < 1:
         raise RuntimeError("checkpoint_group_size must be >= 1")
-    return _Dims(B, NH, NC, CS, F, G, code, _state["impl"], _state["eps"])
+    return _Dims(B, NH, NC, CS, F, G, code, _impl_code(impl), _state["eps"])
 
 
 # Workspaces (the TTT-MLP backward's step records: 2.2 GB at 48 heads) are kept per (device, stream) and grown on demand instead of
@@ -343,10 +352,12 @@ def _launch(fn_name: str, dims: _Dims, args, device, suffix: str = "", extra=())
         raise RuntimeError(lib.ttt_hip_last_error().decode())
 
 
-def resolved_impl(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, mlp=True, backward=False) -> str:
-    """Name of the kernel family a call with these dims would run ('generic' / 'mfma')."""
+def resolved_impl(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, mlp=True, backward=False, *, impl=None) -> str:
+    """Name of the kernel family a call with these dims would run ('generic' / 'mfma'; 'unsupported': the selector asks for a family
+    that has no kernel for them).  ``impl``: the selector of this question instead of the global one - e.g. ``impl="mfma"`` asks
+    whether an explicit request would be accepted (TTT-Linear at mini-batches of 64: 'mfma' on request, 'generic' under 'auto')."""
     lib = load_library()
-    d = _dims(B, NH, NC, CS, F, G, act_dtype)
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
     r = lib.ttt_hip_resolve_impl(ctypes.byref(d), int(mlp), int(backward))
     return {1: "generic", 2: "mfma"}.get(r, "unsupported")
 
@@ -365,15 +376,16 @@ def _fill_args(struct, spec, tensors, sizes, act, optional=()):
     return struct(*ptrs)
 
 
-def _scan_args(struct, spec, tensors, checkpoint_group_size, optional=()):
-    """(dims, args, device) of one scan op for ``_launch``: the sizes are XQ's, the tensors are checked against ``spec``"""
+def _scan_args(struct, spec, tensors, checkpoint_group_size, optional=(), impl=None):
+    """(dims, args, device) of one scan op for ``_launch``: the sizes are XQ's, the tensors are checked against ``spec``; ``impl``
+    overrides the global selector for this call"""
     XQ = tensors[0]
     _check5(XQ)
     B, NH, NC, CS, F = XQ.shape
     G = int(checkpoint_group_size)
     sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
     args = _fill_args(struct, spec, tensors, sizes, XQ.dtype, optional)
-    return _dims(B, NH, NC, CS, F, G, XQ.dtype), args, XQ.device
+    return _dims(B, NH, NC, CS, F, G, XQ.dtype, impl), args, XQ.device
 
 
 def ttt_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
@@ -420,8 +432,18 @@ def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkp
 def ttt_linear_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,
                        b1_checkpoints, XQW_batch, checkpoint_group_size):
     """TTT-Linear forward scan (replaces ttt_linear_scan_forward, linear_triton.py:98-129)."""
+    ttt_linear_forward_impl(None, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,
+                            b1_checkpoints, XQW_batch, checkpoint_group_size)
+
+
+def ttt_linear_forward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,
+                            b1_checkpoints, XQW_batch, checkpoint_group_size):
+    """``ttt_linear_forward`` with the selector of THIS call: ``impl`` None (the global selector) or 'auto' / 'generic' / 'mfma' -
+    'mfma' at mini-batches of 64 runs the opt-in MFMA scan of csrc/ttt_lin64_body.h.  (A function of its own, not a keyword of
+    ``ttt_linear_forward``: that one keeps the parameter list of the reference's launch site, which tests/test_reference_tkmlp_cpu.py
+    counts.)"""
     tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints, b1_checkpoints, XQW_batch)
-    _launch("ttt_hip_linear_forward", *_scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size))
+    _launch("ttt_hip_linear_forward", *_scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl))
 
 
 def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
@@ -429,10 +451,20 @@ def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1
                         grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
                         grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
     """TTT-Linear backward (replaces ttt_linear_scan_backward, linear_triton.py:203-246)."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last,
-               grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias,
-               grad_L_W1_init, grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    _launch("ttt_hip_linear_backward", *_scan_args(_LinBwd, _LIN_BWD_SPEC, tensors, checkpoint_group_size))
+    ttt_linear_backward_impl(None, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last,
+                             grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias,
+                             grad_L_W1_init, grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size)
+
+
+def ttt_linear_backward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
+                             grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
+                             grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
+                             grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
+    """``ttt_linear_backward`` with the selector of this call (see ``ttt_linear_forward_impl``)."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
+               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
+               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    _launch("ttt_hip_linear_backward", *_scan_args(_LinBwd, _LIN_BWD_SPEC, tensors, checkpoint_group_size, impl=impl))
 
 
 # ------------------------------------------------------------------------------------------------

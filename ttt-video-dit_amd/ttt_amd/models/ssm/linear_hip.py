@@ -9,6 +9,7 @@ Activations may be bf16 or fp32 (the Triton path accepts both); state and checkp
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -20,8 +21,27 @@ def _ext():
     return test_time_training
 
 
+def _cs64_impl_default():
+    v = os.environ.get("TTT_LINEAR_CS64_IMPL", "auto")
+    if v not in ("auto", "mfma"):
+        raise ValueError(f"TTT_LINEAR_CS64_IMPL: expected 'auto' or 'mfma', got {v!r}")
+    return v
+
+
 class HipLinear(torch.autograd.Function):
     sharded_mode = False
+    # Kernels of the calls at mini-batches of 64 with bf16 activations and head_dim 64: "auto" = what the library's selector picks
+    # (the generic fp32-arithmetic kernels), "mfma" = the opt-in MFMA scan and sweep (csrc/ttt_lin64_body.h).  Every other call
+    # is untouched.  Default from the environment variable TTT_LINEAR_CS64_IMPL, read once at import.
+    cs64_impl = _cs64_impl_default()
+
+    @staticmethod
+    def _impl(CS, F, act):
+        if HipLinear.cs64_impl == "mfma" and CS == 64 and F == 64 and act == torch.bfloat16:
+            return "mfma"
+        if HipLinear.cs64_impl not in ("auto", "mfma"):
+            raise ValueError(f"HipLinear.cs64_impl: expected 'auto' or 'mfma', got {HipLinear.cs64_impl!r}")
+        return None
 
     @staticmethod
     def forward(ctx, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, XQ_batch, XV_batch, XK_batch, eta_batch,
@@ -39,7 +59,11 @@ class HipLinear(torch.autograd.Function):
         out = torch.empty(B, NH, NC, CS, F, device=dev, dtype=act)
         W1c = torch.empty(B, NH, K, F, F, device=dev, dtype=_F32)
         b1c = torch.empty(B, NH, K, 1, F, device=dev, dtype=_F32)
-        ext.ttt_linear_forward(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, out, G)
+        # the backward runs the family the forward ran ; None: the plain call, which is all that the oracle-backed stand-in of
+        # the CPU tests (oracle/cpu_ext.py) provides
+        ctx.impl = HipLinear._impl(CS, F, act)
+        fwd = ext.ttt_linear_forward if ctx.impl is None else (lambda *a: ext.ttt_linear_forward_impl(ctx.impl, *a))
+        fwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, out, G)
         ctx.save_for_backward(XQ, XV, XK, last_eta, ln_w, ln_b, W1c, b1c)
         ctx.G = G
         ctx.eta_shape = tuple(eta_batch.shape)
@@ -59,8 +83,9 @@ class HipLinear(torch.autograd.Function):
         dW1, db1 = e32(B, NH, F, F), e32(B, NH, 1, F)
         d_eta = torch.empty(B, NH, NC, CS, 1, device=dev, dtype=act)
         dQ, dK, dV = (torch.empty_like(XQ) for _ in range(3))
-        ext.ttt_linear_backward(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
-                                d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV, G)
+        bwd = ext.ttt_linear_backward if ctx.impl is None else (lambda *a: ext.ttt_linear_backward_impl(ctx.impl, *a))
+        bwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
+            d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV, G)
         ln_dt, st_dt = ctx.param_dtypes
         row = d_eta.transpose(-2, -1)
         rows = ctx.eta_shape[-2]

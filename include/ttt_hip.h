@@ -173,6 +173,8 @@ int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* wor
 int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                               float* W2_final, float* b2_final, void* workspace, size_t workspace_bytes, void* stream);
 int ttt_hip_linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* workspace, size_t workspace_bytes, void* stream);
+/* (The TTT-Linear forward over a part of the sequence, the counterpart of the _chunk entry above, is declared in a second header,
+ * ttt_hip_parts.h: extensions beside the reference's operator boundary; this header keeps its 46 functions.) */
 int ttt_hip_linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Fused pre- / post-processing of the TTT layer (bf16 activations, head_dim 64) ---------------------------

@@ -11,6 +11,12 @@ The sampling geometry (mini-batches of 16, one checkpoint group, the guidance pa
 
 ("default" = the library's plan; at mini-batches of 16 a number means exactly that many parts).  --scan-only times the scans
 alone: the one-call forward against the same scan as the chunk launches of each plan, back to back on one stream.
+
+The TTT-Linear layer (--ssm ttt_linear; --parts sets TTTBase.linear_pipeline_parts, "default" = off; mini-batches of 64 run in parts
+on the opt-in MFMA scan only, --cs64-impl mfma; mini-batches of 16 have an MFMA backward, so --no-grad is optional there):
+
+    python tools/ttt_layer_bench.py --ssm ttt_linear --cs64-impl mfma --no-grad --parts 0,2,4,8
+    python tools/ttt_layer_bench.py --ssm ttt_linear --mini-batch 16 --batch 2 --no-grad --video-length 63sec --parts 0,4,8 [--scan-only]
 """
 import argparse
 import json
@@ -36,6 +42,7 @@ def timeit(fn, iters=3):
 def scan_only(a, ext, layer, meta, x, L, parts, set_parts, res):
     """the scan kernels alone at this geometry (random inputs): ttt_forward against the chunk launches of each plan"""
     dev = x.device
+    mlp = a.ssm == "ttt_mlp"
     B, NH, CS, Fh = x.shape[0], layer.ttt.num_heads, a.mini_batch, 64
     NC = L // CS
     G = layer.ttt._group_size(NC)
@@ -45,19 +52,28 @@ def scan_only(a, ext, layer, meta, x, L, parts, set_parts, res):
     l2 = lambda t: torch.nn.functional.normalize(t, dim=-1)
     XQ, XK, XV = l2(mk(B, NH, NC, CS, Fh)).bfloat16(), l2(mk(B, NH, NC, CS, Fh)).bfloat16(), mk(B, NH, NC, CS, Fh, scale=0.5).bfloat16()
     eta = (torch.rand(B, NH, NC, CS, 1, device=dev, generator=g) * 0.02 + 0.005).bfloat16()
-    lw, lb = (1 + 0.1 * mk(1, NH, 1, Fh)).float(), (0.1 * mk(1, NH, 1, Fh)).float()
-    st = [mk(B, NH, Fh, 4 * Fh, scale=0.02), mk(B, NH, 1, 4 * Fh, scale=0.02), mk(B, NH, 4 * Fh, Fh, scale=0.02), mk(B, NH, 1, Fh, scale=0.02)]
-    e32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    cks = (e32(B, NH, K, Fh, 4 * Fh), e32(B, NH, K, 1, 4 * Fh), e32(B, NH, K, 4 * Fh, Fh), e32(B, NH, K, 1, Fh))
+    ln_shape = (1, NH, 1, Fh) if mlp else (NH, Fh)
+    lw, lb = (1 + 0.1 * mk(*ln_shape)).float(), (0.1 * mk(*ln_shape)).float()
+    shapes = ((Fh, 4 * Fh), (1, 4 * Fh), (4 * Fh, Fh), (1, Fh)) if mlp else ((Fh, Fh), (1, Fh))
+    st = [mk(B, NH, *sh, scale=0.02) for sh in shapes]
+    cks = tuple(torch.empty(B, NH, K, *sh, device=dev, dtype=torch.float32) for sh in shapes)
     out0, out1 = torch.empty_like(XQ), torch.empty_like(XQ)
+    if mlp:
+        scan, scan_chunk = ext.ttt_forward, ext.ttt_forward_chunk
+    else:
+        from ttt_amd.models.ssm.linear_hip import HipLinear
+        impl = HipLinear._impl(CS, Fh, torch.bfloat16)
+        res["scan_impl"] = ext.resolved_impl(B, NH, NC, CS, Fh, G, torch.bfloat16, mlp=False, backward=False, impl=impl)
+        scan = lambda *t: ext.ttt_linear_forward_impl(impl, *t)
+        scan_chunk = lambda *t: ext.ttt_linear_forward_chunk(impl, *t)
 
     def one_call():
-        ext.ttt_forward(XQ, XK, XV, eta, lw, lb, *st, *cks, out0, G)
+        scan(XQ, XK, XV, eta, lw, lb, *st, *cks, out0, G)
 
     def in_parts(plan):
         carry = [t.clone() for t in st]
         for s0, ns, _ in plan:
-            ext.ttt_forward_chunk(XQ, XK, XV, eta, lw, lb, *carry, *cks, out1, G, s0, ns)
+            scan_chunk(XQ, XK, XV, eta, lw, lb, *carry, *cks, out1, G, s0, ns)
 
     plans = {}
     for n in parts:
@@ -88,6 +104,8 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--no-grad", action="store_true", help="forward only (required at mini-batches of 16: no MFMA backward there)")
     ap.add_argument("--scan-only", action="store_true", help="time the scan kernels alone: one call against the parts of each plan")
+    ap.add_argument("--ssm", default="ttt_mlp", choices=["ttt_mlp", "ttt_linear"], help="ttt_linear: --parts sets linear_pipeline_parts")
+    ap.add_argument("--cs64-impl", default=None, choices=["auto", "mfma"], help="HipLinear.cs64_impl for the whole run (TTT-Linear at mini-batches of 64)")
     ap.add_argument("--tuning-file", default=None, help="GEMM solution selections to load instead of the committed ttt_amd/infra/gemm_tuning_gfx950.csv")
     ap.add_argument("--debug-option", action="append", default=[], metavar="NAME=VALUE", help="library debug option(s) for the whole run (e.g. scan_pair=0)")
     a = ap.parse_args()
@@ -102,10 +120,16 @@ def main():
         ext.debug_option(kv.split("=")[0], int(kv.split("=")[1]))
     dev = torch.device("cuda:0")
     tuned = enable_tuned_gemms(a.tuning_file)
-    if a.mini_batch == 16 and not a.no_grad:
+    linear = a.ssm == "ttt_linear"
+    if a.mini_batch == 16 and not a.no_grad and not linear:
         ap.error("--mini-batch 16 needs --no-grad")
-    over = {"mini_batch_size": 16, "scan_checkpoint_group_size": 10 ** 6} if a.mini_batch == 16 else {}
-    cfg = ModelConfig.get_preset("5B", a.video_length, ssm_layer="ttt_mlp", adapter_method="qkvo", **over)
+    from ttt_amd.models.ssm.linear_hip import HipLinear
+    if a.cs64_impl is not None:
+        HipLinear.cs64_impl = a.cs64_impl
+    over = {"mini_batch_size": 16} if a.mini_batch == 16 else {}
+    if a.mini_batch == 16 and a.no_grad:
+        over["scan_checkpoint_group_size"] = 10 ** 6          # the evaluation settings: no scan checkpoints
+    cfg = ModelConfig.get_preset("5B", a.video_length, ssm_layer=a.ssm, adapter_method="qkvo", **over)
     frames, tl = cfg.compressed_num_frames, TEXT_LEN[a.video_length]
     scenes = max((frames - 1) // 12, 1)
     n_vid = frames * TOKENS_PER_FRAME
@@ -123,11 +147,16 @@ def main():
     dy = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16() * 0.1
     params = [p for p in layer.parameters() if p.requires_grad]
     parts = [v if v == "default" else int(v) for v in a.parts.split(",")]
-    res = {"L": L, "batch": a.batch, "mini_batch": a.mini_batch, "tuned_gemms": bool(tuned), "by_parts": {}}
+    res = {"L": L, "batch": a.batch, "mini_batch": a.mini_batch, "ssm": a.ssm, "tuned_gemms": bool(tuned), "by_parts": {}}
+    if linear:
+        res["cs64_impl"] = HipLinear.cs64_impl
     default_plan = (layer.ttt.pipeline_parts, layer.ttt.pipeline_parts_auto)
+    default_linear = layer.ttt.linear_pipeline_parts
 
     def set_parts(n):
-        if n == "default":
+        if linear:
+            layer.ttt.linear_pipeline_parts = default_linear if n == "default" else n
+        elif n == "default":
             layer.ttt.pipeline_parts, layer.ttt.pipeline_parts_auto = default_plan
         else:
             layer.ttt.pipeline_parts = n
@@ -178,6 +207,9 @@ def main():
     for n in parts:
         med = {k: sorted(v)[len(v) // 2] for k, v in t[n].items()}
         ent = {"median_ms": med}
+        set_parts(n)
+        plan = layer.ttt._pipeline_plan(x, meta, L, False, False)
+        ent["part_steps"] = None if plan is None else [p[1] for p in plan]
         if n != parts[0]:
             for rev in (False, True):
                 y, gr = fwd_bwd(n, rev)

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
-#include "../../include/ttt_hip.h"
+#include "../../include/ttt_hip_parts.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -223,6 +223,23 @@ int ttt_hip_linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void
     if (r == TTT_IMPL_MFMA) ttt::mfma::linear_forward(d, a, ws, (hipStream_t)stream);
     else ttt::generic::linear_forward(d, a, ws, (hipStream_t)stream);
     return post_launch("linear_forward");
+}
+
+// include/ttt_hip_parts.h
+int ttt_hip_linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
+                                 void*, size_t, void* stream) {
+    if (check_dims(d)) return -1;
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(W1_init); NEED(b1_init); NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(XQW);
+    // (fp32 activations, TTT_IMPL_GENERIC and mini-batches of 64 under TTT_IMPL_AUTO resolve to the generic kernels)
+    if (resolve(d, false, false) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
+        return fail("ttt_hip: linear_forward_chunk: only the MFMA scan (mini-batches of 16; of 64 on an explicit TTT_IMPL_MFMA) continues from a state");
+    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
+        return fail("ttt_hip: linear_forward_chunk: the part [step0, step0 + nsteps) must lie inside [0, NC)");
+    if (!W1_final != !b1_final) return fail("ttt_hip: linear_forward_chunk: give both final-state buffers or neither");
+    ttt::mfma::linear_forward_chunk(d, a, step0, nsteps, W1_final, b1_final, (hipStream_t)stream);
+    return post_launch("linear_forward_chunk");
 }
 
 int ttt_hip_linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* ws, size_t wsb, void* stream) {

@@ -163,11 +163,15 @@ TTT_WV_FN void inner_grad(BK& bk, const f32x4 (&z)[4], const f32x4 (&tg)[4], con
 }
 
 // ===================================================================================================================
-// forward scan of (b, h) = bh
+// forward scan of (b, h) = bh over the steps [c.step0, c.step0 + c.p.NC) of a scan of c.NCs steps (Lin16ChunkParams,
+// ttt_wave_types.h).  `it` counts the steps of the part; tiles and checkpoints are addressed in the whole sequence.  The
+// hand-over between parts is the fp32 state the wave holds (W1t, b1v): the packed W1F is rebuilt from it every step, so a part
+// that starts at any step reproduces the bits of the one-call scan.
 template <class BK>
-TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
+TTT_WV_FN void forward_part(BK& bk, const Lin16ChunkParams& c, int bh) {
+    const Lin16Params& p = c.p;
     const int l0 = bk.lane();
-    const int NC = p.NC, G = p.G, head = bh % p.NH;
+    const int NC = p.NC, G = p.G, head = bh % p.NH, step0 = c.step0;
 
     f32x4 W1t[4][4];     // [fa][fb]  W1[16fa + 4g + r][16fb + i]     (rows = f_in, lane = f_out)
     float b1v[4], gam[4], bet[4];
@@ -203,7 +207,7 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
 #pragma unroll
         for (int fb = 0; fb < 4; ++fb) W1F[ks][fb] = stack(W1t[2 * ks][fb], W1t[2 * ks + 1][fb]);
 
-    const size_t tile0 = (size_t)bh * NC;
+    const size_t tile0 = (size_t)bh * c.NCs + step0;
     Stage sk, sv, sq;
     unsigned short pe;
     stage_request(bk, sk, p.XK + tile0 * 1024);
@@ -226,8 +230,8 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
             stage_request(bk, sq, p.XQ + tn * 1024);
             pe = *reinterpret_cast<const unsigned short*>(p.eta + tn * 16 + (l & 15));
         }
-        if (it % G == 0) {      // checkpoint: state entering step `it` (linear_triton.py:84-97)
-            const size_t ck = (size_t)bh * p.K + it / G;
+        if ((step0 + it) % G == 0) {      // checkpoint: state entering step `step0 + it` (linear_triton.py:84-97)
+            const size_t ck = (size_t)bh * p.K + (step0 + it) / G;
             float* W1g = p.W1c + ck * 64 * 64;
 #pragma unroll
             for (int fa = 0; fa < 4; ++fa)
@@ -294,6 +298,30 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
         if (l < 16) bk.template lds<float>(L_ETA + (nb * 16 + l) * 4) = (float)*reinterpret_cast<const __bf16*>(&pe);
         bk.lds_fence();
     }
+    if (c.W1f) {      // hand the state on.  May overwrite the initial state: this wave is the only reader of its (b, h)'s p.W1 /
+                      // p.b1 and read all of it before the first step.  (Lane indices of its own: the loop's are not kept alive.)
+        const int l = bk.opaque(l0), g = l >> 4, i = l & 15;
+        float* W1g = c.W1f + (size_t)bh * 64 * 64;
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) W1g[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * fb + i] = W1t[fa][fb][r];
+        if (g == 0)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) c.b1f[(size_t)bh * 64 + 16 * fb + i] = b1v[fb];
+    }
+}
+// the whole sequence in one call: the part [0, NC) without a final-state store
+template <class BK>
+TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
+    Lin16ChunkParams c;
+    c.p = p;
+    c.step0 = 0;
+    c.NCs = p.NC;
+    c.W1f = c.b1f = nullptr;
+    forward_part(bk, c, bh);
 }
 
 // ===================================================================================================================

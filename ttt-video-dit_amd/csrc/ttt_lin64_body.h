@@ -185,17 +185,21 @@ TTT_WV_FN void inner_publish(BK& bk, int w, int Kt, int Vt, int eta_off, const b
 }
 
 // ===================================================================================================================
-// forward scan of (b, h) = bh ; the four waves of the workgroup call it together
+// forward scan of (b, h) = bh over the steps [c.step0, c.step0 + c.p.NC) of a scan of c.NCs steps (Lin16ChunkParams,
+// ttt_wave_types.h) ; the four waves of the workgroup call it together.  The hand-over between parts is the fp32 state (every
+// wave its slice W1t, all of them b1v): the L_WI image is published from it before the first step and after every update, so a
+// part that starts at any step reproduces the bits of the one-call scan.
 template <class BK>
-TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
+TTT_WV_FN void forward_part(BK& bk, const Lin16ChunkParams& c, int bh) {
+    const Lin16Params& p = c.p;
     const int l0 = bk.lane(), w = bk.wave();
-    const int NC = p.NC, G = p.G, head = bh % p.NH;
+    const int NC = p.NC, G = p.G, head = bh % p.NH, step0 = c.step0;
     const int IMG = L_IMG + w * 2 * IMG_BYTES, ETA = L_ETA + w * 128, own = w * TILE_B;
 
     f32x4 W1t[4];        // [fa]  W1[16fa + 4g + r][16w + i]
     float b1v[4];
-    Consts c;
-    make_consts(bk, p, head, c);
+    Consts k;
+    make_consts(bk, p, head, k);
     {
         const int g = l0 >> 4, i = l0 & 15;
         const float* W1g = p.W1 + (size_t)bh * 64 * 64;
@@ -206,7 +210,7 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
 #pragma unroll
         for (int fb = 0; fb < 4; ++fb) b1v[fb] = p.b1[(size_t)bh * 64 + 16 * fb + i];
     }
-    const size_t tile0 = (size_t)bh * NC;
+    const size_t tile0 = (size_t)bh * c.NCs + step0;
     Stage sk, sv, sq;
     unsigned short pe;
     lin16::stage_request(bk, sk, p.XK + tile0 * 4096 + w * 1024);
@@ -231,8 +235,8 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
             lin16::stage_request(bk, sq, p.XQ + tn * 4096 + w * 1024);
             pe = *reinterpret_cast<const unsigned short*>(p.eta + tn * 64 + 16 * w + (l & 15));
         }
-        if (it % G == 0) {      // checkpoint: state entering step `it` ; wave w its slice, wave 0 the bias
-            const size_t ck = (size_t)bh * p.K + it / G;
+        if ((step0 + it) % G == 0) {      // checkpoint: state entering step `step0 + it` ; wave w its slice, wave 0 the bias
+            const size_t ck = (size_t)bh * p.K + (step0 + it) / G;
             float* W1g = p.W1c + ck * 64 * 64;
 #pragma unroll
             for (int fa = 0; fa < 4; ++fa)
@@ -242,7 +246,7 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
 #pragma unroll
                 for (int fb = 0; fb < 4; ++fb) p.b1c[ck * 64 + 16 * fb + i] = b1v[fb];
         }
-        inner_publish(bk, w, L_K + buf * T64_B + own, L_V + buf * T64_B + own, ETA + buf * 64, Wp, b1v, c, p.eps);
+        inner_publish(bk, w, L_K + buf * T64_B + own, L_V + buf * T64_B + own, ETA + buf * 64, Wp, b1v, k, p.eps);
         bk.barrier();                                                   // A: L_X, L_PS written | read
         update_slice(bk, w, L_K + buf * T64_B, L_X, L_PS, W1t, b1v);    // W1 += K^T Gs ; b1 += colsum Gs
         publish_slice(bk, w, W1t, mine);
@@ -258,11 +262,11 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
                 a = bk.mma32(qA0, Wp[fb], a);
                 a = bk.mma32(qA1, Wp[4 + fb], a);
                 y[fb] = a + b1v[fb];
-                qc[fb] = bk.mma16(c.IDP, lin16::tr4(bk, Qt, TS, 0, 16 * fb), zero4());
+                qc[fb] = bk.mma16(k.IDP, lin16::tr4(bk, Qt, TS, 0, 16 * fb), zero4());
             }
             lin16::normalize_rows(bk, y, p.eps);
 #pragma unroll
-            for (int fb = 0; fb < 4; ++fb) y[fb] = qc[fb] + c.gam[fb] * y[fb] + c.bet[fb];
+            for (int fb = 0; fb < 4; ++fb) y[fb] = qc[fb] + k.gam[fb] * y[fb] + k.bet[fb];
             lin16::store_rows(bk, IMG, y, p.out + tile * 4096 + w * 1024);
         }
         // the other buffer's K tiles were last read by other waves before B of the step before this one
@@ -270,6 +274,32 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
         park_eta(bk, pe, ETA + nb * 64);
         bk.lds_fence();
     }
+    if (c.W1f) {      // hand the state on: wave w its column slice, wave 0 the bias, as the checkpoint store does.
+        // W1f / b1f MAY ALIAS p.W1 / p.b1 (the pipeline carries the state in place).  Global memory, so the emulator's race detector
+        // does not see this one; it rests on the barriers: all four waves read b1 and their own W1 slice before the first barrier
+        // (in front of the step loop), and these stores come behind barriers A and B of the last step - no wave can still be
+        // reading the initial state, and a wave overwrites only the slice that it alone read.  (Lane indices of its own, so that
+        // the store keeps nothing alive across the step loop.)
+        const int l = bk.opaque(l0), g = l >> 4, i = l & 15;
+        float* W1g = c.W1f + (size_t)bh * 64 * 64;
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) W1g[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * w + i] = W1t[fa][r];
+        if (w == 0 && g == 0)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) c.b1f[(size_t)bh * 64 + 16 * fb + i] = b1v[fb];
+    }
+}
+// the whole sequence in one call: the part [0, NC) without a final-state store
+template <class BK>
+TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
+    Lin16ChunkParams c;
+    c.p = p;
+    c.step0 = 0;
+    c.NCs = p.NC;
+    c.W1f = c.b1f = nullptr;
+    forward_part(bk, c, bh);
 }
 
 // ===================================================================================================================

@@ -15,6 +15,8 @@ void mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, 
                        void* ws, hipStream_t s);          // CS = 64 only; ws: the forward workspace or null (one workgroup per (b,h))
 int  mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, hipStream_t s);   // 0, or < 0: no kernel was launched
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* ws, hipStream_t s);
+void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f,
+                          hipStream_t s);                    // CS = 16 or 64; any [step0, step0 + nsteps) inside [0, NC)
 void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* ws, hipStream_t s);
 }  // namespace mfma
 }  // namespace ttt

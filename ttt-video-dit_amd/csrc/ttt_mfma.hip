@@ -55,16 +55,24 @@ void mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, 
     if (cs16) launch_scan_forward_cs16(p, d->B * d->NH, g_dbg, s);
     else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
 }
-void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipStream_t s) {
-    wv::Lin16Params p = {};
+// steps [step0, step0 + nsteps) of the TTT-Linear scan: the same kernel over a part of the sequence, started from the state in
+// a->W1_init / b1_init, its checkpoints written at their places in the whole sequence's arrays, the state after its last step
+// left in W1f / b1f (both null: not stored).  Parts start at any step at both mini-batch sizes (ttt_wave_types.h).
+void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, hipStream_t s) {
+    wv::Lin16ChunkParams c = {};
+    wv::Lin16Params& p = c.p;
     p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
     p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
     p.W1 = a->W1_init; p.b1 = a->b1_init;
     p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints;
     p.out = (__bf16*)a->XQW;
-    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    if (d->CS == 16) launch_linear_forward_cs16(p, d->B * d->NH, s);
-    else launch_linear_forward_cs64(p, d->B * d->NH, s);
+    p.NH = d->NH; p.NC = nsteps; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    c.step0 = step0; c.NCs = d->NC; c.W1f = W1f; c.b1f = b1f;
+    if (d->CS == 16) launch_linear_forward_cs16(c, d->B * d->NH, s);
+    else launch_linear_forward_cs64(c, d->B * d->NH, s);
+}
+void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipStream_t s) {
+    linear_forward_chunk(d, a, 0, d->NC, nullptr, nullptr, s);
 }
 void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hipStream_t s) {
     wv::Lin16Params p = {};

@@ -135,13 +135,14 @@ struct DeviceWave {
 constexpr int LIN_WAVES = 4;
 constexpr int LDS_LIN = LIN_WAVES * lin16::WAVE_LDS;
 
-__global__ __launch_bounds__(64 * LIN_WAVES) void linear_scan16_kernel(wv::Lin16Params p, int n_bh) {
+// (the whole sequence or a part of it - one kernel for both: the one-call scan is the part [0, NC) without a final-state store)
+__global__ __launch_bounds__(64 * LIN_WAVES) void linear_scan16_kernel(wv::Lin16ChunkParams c, int n_bh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int bh = blockIdx.x * LIN_WAVES + w;
     if (bh >= n_bh) return;                                          // whole wave; no barriers in this kernel
     DeviceWave bk{smem + w * lin16::WAVE_LDS};
-    lin16::forward(bk, p, bh);
+    lin16::forward_part(bk, c, bh);
 }
 
 // TTT-MLP forward scan at mini-batches of 16: the backend-templated workgroup body of ttt_mlp16_body.h, over the whole sequence
@@ -160,11 +161,12 @@ __global__ __launch_bounds__(64) void linear_bwd16_kernel(wv::Lin16Params p) {
 }
 
 // TTT-Linear at mini-batches of 64 tokens (ttt_lin64_body.h): one workgroup of four waves per (b, h), one wave per SIMD - up to 512
-// registers per lane.  Runs on an explicit TTT_IMPL_MFMA only (capi.hip: resolve()).
-__global__ __launch_bounds__(64 * lin64::WAVES) void linear_fwd_cs64_kernel(wv::Lin16Params p) {
+// registers per lane.  Runs on an explicit TTT_IMPL_MFMA only (capi.hip: resolve()).  The forward kernel serves the one-call scan
+// and the scan in parts alike, as at mini-batches of 16.
+__global__ __launch_bounds__(64 * lin64::WAVES) void linear_fwd_cs64_kernel(wv::Lin16ChunkParams c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     DeviceWave bk{smem};
-    lin64::forward(bk, p, blockIdx.x);
+    lin64::forward_part(bk, c, blockIdx.x);
 }
 __global__ __launch_bounds__(64 * lin64::WAVES) void linear_bwd_cs64_kernel(wv::Lin16Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -181,10 +183,10 @@ static void lin_attr_once() {
         (void)hipFuncSetAttribute((const void*)v16::linear_bwd16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS_BWD);
     });
 }
-void launch_linear_forward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
+void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
     lin_attr_once();
     const int blocks = (n_bh + v16::LIN_WAVES - 1) / v16::LIN_WAVES;
-    hipLaunchKernelGGL(v16::linear_scan16_kernel, dim3(blocks), dim3(64 * v16::LIN_WAVES), v16::LDS_LIN, s, p, n_bh);
+    hipLaunchKernelGGL(v16::linear_scan16_kernel, dim3(blocks), dim3(64 * v16::LIN_WAVES), v16::LDS_LIN, s, c, n_bh);
 }
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
     lin_attr_once();
@@ -198,9 +200,9 @@ static void lin64_attr_once() {
         (void)hipFuncSetAttribute((const void*)v16::linear_bwd_cs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::GROUP_LDS_BWD);
     });
 }
-void launch_linear_forward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
+void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
     lin64_attr_once();
-    hipLaunchKernelGGL(v16::linear_fwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS, s, p);
+    hipLaunchKernelGGL(v16::linear_fwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS, s, c);
 }
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
     lin64_attr_once();

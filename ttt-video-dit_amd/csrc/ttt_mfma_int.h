@@ -46,9 +46,9 @@ int device_cu_count();                // compute units of the current device (ca
 int get_debug_fast_records();
 // mini-batches of 16 tokens, forward only (ttt_mfma16.hip): the evaluation / sampling geometry
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long* dbg, hipStream_t s);
-void launch_linear_forward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h)
+void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h); whole sequence or a part
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
-void launch_linear_forward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h)
+void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h); whole sequence or a part
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void set_debug_dump(float* buf);
 unsigned long long* get_debug_timing();

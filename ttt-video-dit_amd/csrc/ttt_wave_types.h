@@ -32,6 +32,18 @@ struct Lin16Params {
     float eps;
 };
 
+// the TTT-Linear forward scan (mini-batches of 16: ttt_lin16_body.h, of 64: ttt_lin64_body.h) over a PART of the sequence: steps
+// [step0, step0 + p.NC) of a sequence of NCs steps.  The pointers of `p` are those of the whole sequence (consecutive heads NCs
+// tiles apart, p.K = ceil(NCs / G) checkpoints per head); p.W1, p.b1 hold the state entering step0; the state after the last
+// step of the part goes to W1f, b1f (layout of the initial state, may alias it; both null: not stored).  A part starts at any
+// step: the kernels hold the whole state in fp32 and rebuild everything else a step takes from its predecessor from it.
+// step0 = 0, NCs = p.NC, no final state: the one-call scan.
+struct Lin16ChunkParams {
+    Lin16Params p;
+    int step0, NCs;
+    float *W1f, *b1f;
+};
+
 // arguments of the TTT-MLP forward scan at mini-batches of 16 tokens (F = 64, hidden 256)
 struct Mlp16Params {
     const __bf16 *XQ, *XK, *XV, *eta;

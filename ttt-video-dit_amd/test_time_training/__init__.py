@@ -148,6 +148,11 @@ _PROTOTYPES = {
     "ttt_hip_resgate_forward": _sig("4i 7p"), "ttt_hip_resgate_backward": _sig("4i 7p"), "ttt_hip_resgate_backward_partials": _sig("i"),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+# ... and of every symbol declared in include/ttt_hip_parts.h, the second header: extensions beside the reference's operator boundary
+# (tests/test_abi_parts_cpu.py compares the two).  EXPORTED_SYMBOLS stays the set of the main header.
+_PROTOTYPES_PARTS = {
+    "ttt_hip_linear_forward_chunk": _sig("2p 2i 3p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -169,7 +174,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(_LIB_PATH)
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
-    for name, (restype, argtypes) in _PROTOTYPES.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -444,6 +449,19 @@ def ttt_linear_forward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_nor
     counts.)"""
     tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints, b1_checkpoints, XQW_batch)
     _launch("ttt_hip_linear_forward", *_scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl))
+
+
+def ttt_linear_forward_chunk(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W1_checkpoints,
+                             b1_checkpoints, XQW_batch, checkpoint_group_size, step0, nsteps):
+    """The TTT-Linear forward over steps [step0, step0 + nsteps) of the sequence the (whole-sequence) tensors describe
+    (``ttt_hip_linear_forward_chunk``, include/ttt_hip_parts.h): started from the fp32 state in ``W1_state`` [B,NH,F,F] / ``b1_state``
+    [B,NH,1,F], which it REPLACES by the state after its last step, so that consecutive calls walk the sequence with the bits of the
+    one-call forward.  MFMA scan only - mini-batches of 16, or of 64 with ``impl='mfma'`` (``impl`` as in ``ttt_linear_forward_impl``) -;
+    a part is any [step0, step0 + nsteps) inside [0, NC) at either mini-batch size."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W1_checkpoints, b1_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl)
+    # the final state goes where the initial one came from
+    _launch("ttt_hip_linear_forward", dims, args, device, suffix="_chunk", extra=(int(step0), int(nsteps), args.W1_init, args.b1_init))
 
 
 def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,

@@ -64,8 +64,11 @@ class FusedPre(torch.autograd.Function):
         B, L, D = XQ_raw.shape
         q, k, v = XQ_raw.contiguous(), XK_raw.contiguous(), XV_raw.contiguous()
         w32, b32 = _f32(ln_w), _f32(ln_b)
-        outs = [torch.empty(B, NH, L, D // NH, device=q.device, dtype=_BF16) for _ in range(3)]
-        ext.pre_forward(q, k, v, rope, src, pos, w32, b32, *outs, NH, n_pos=getattr(pos, "_ttt_max_pos", None))
+        from ttt_amd.models.ssm.pipeline import injected
+        outs = injected("pre")               # (a pipelined TTT-Linear forward has pre-processed the sequence part by part already)
+        if outs is None:
+            outs = [torch.empty(B, NH, L, D // NH, device=q.device, dtype=_BF16) for _ in range(3)]
+            ext.pre_forward(q, k, v, rope, src, pos, w32, b32, *outs, NH, n_pos=getattr(pos, "_ttt_max_pos", None))
         ctx.save_for_backward(q, k, v, w32, rope, src, pos)
         ctx.NH, ctx.param_dtype = NH, ln_w.dtype
         return tuple(outs)

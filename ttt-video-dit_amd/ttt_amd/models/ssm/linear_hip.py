@@ -55,15 +55,20 @@ class HipLinear(torch.autograd.Function):
         last_eta = eta_batch.to(act)[:, :, :, -1, :, None].contiguous()   # kernels/linear_forward.py:90-101
         ln_w = ttt_norm_weight.reshape(NH, F).to(_F32).contiguous()
         ln_b = ttt_norm_bias.reshape(NH, F).to(_F32).contiguous()
-        W1, b1 = W1_init.to(_F32).contiguous(), b1_init.to(_F32).contiguous()
-        out = torch.empty(B, NH, NC, CS, F, device=dev, dtype=act)
-        W1c = torch.empty(B, NH, K, F, F, device=dev, dtype=_F32)
-        b1c = torch.empty(B, NH, K, 1, F, device=dev, dtype=_F32)
         # the backward runs the family the forward ran ; None: the plain call, which is all that the oracle-backed stand-in of
         # the CPU tests (oracle/cpu_ext.py) provides
         ctx.impl = HipLinear._impl(CS, F, act)
-        fwd = ext.ttt_linear_forward if ctx.impl is None else (lambda *a: ext.ttt_linear_forward_impl(ctx.impl, *a))
-        fwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, out, G)
+        from ttt_amd.models.ssm.pipeline import injected
+        pre = injected("scan_lin")            # (a pipelined forward: the scan has walked the sequence part by part already, on the
+        if pre is not None:                   # same kernel family: TTTBase._pipeline_plan asks with this call's selector)
+            out, W1c, b1c = pre
+        else:
+            out = torch.empty(B, NH, NC, CS, F, device=dev, dtype=act)
+            W1c = torch.empty(B, NH, K, F, F, device=dev, dtype=_F32)
+            b1c = torch.empty(B, NH, K, 1, F, device=dev, dtype=_F32)
+            W1, b1 = W1_init.to(_F32).contiguous(), b1_init.to(_F32).contiguous()
+            fwd = ext.ttt_linear_forward if ctx.impl is None else (lambda *a: ext.ttt_linear_forward_impl(ctx.impl, *a))
+            fwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, out, G)
         ctx.save_for_backward(XQ, XV, XK, last_eta, ln_w, ln_b, W1c, b1c)
         ctx.G = G
         ctx.eta_shape = tuple(eta_batch.shape)

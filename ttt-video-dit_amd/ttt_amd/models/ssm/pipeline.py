@@ -1,4 +1,4 @@
-"""The TTT-MLP layer's forward as a pipeline over parts of the sequence (round 5).
+"""The TTT-MLP layer's forward as a pipeline over parts of the sequence (round 5); opt-in, the TTT-Linear layer's too (LIN_QUANTUM below).
 
 The forward scan is sequential and occupies ``B * NH`` = 48 of the 256 CUs for 6.2 ms per call at the 9 s geometry (84 calls per
 training step), with 208 CUs idle; the projections in front of it (``wq / wk / wv``: 2.2 ms, pre-processing 0.4 ms) and behind it
@@ -44,7 +44,8 @@ def side_stream(device) -> torch.cuda.Stream:
 
 # ---- injection: results of the pre-pass that the autograd Functions take instead of computing -----------------------------------
 class injecting:
-    """``with injecting({"linear3": (q, k, v), "scan": (out, *cks), "post": y, "wo": o}): ...`` - every entry must be taken once."""
+    """``with injecting({"linear3": (q, k, v), "scan": (out, *cks), "post": y, "wo": o}): ...`` - every entry must be taken once
+    (TTT-Linear: "pre" and "scan_lin" in the place of "scan")."""
 
     def __init__(self, results):
         self.results = dict(results)
@@ -163,8 +164,36 @@ def plan_parts(src_cpu, L: int, CS: int, G: int, n_parts: int):
     return parts
 
 
-def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n_pos, NH, state, last_eta, G, parts):
-    """Fills and returns {"linear3": (XQr, XKr, XVr), "scan": (out, W1c, b1c, W2c, b2c), "post": y, "wo": o} (no autograd)."""
+# TTT-Linear in parts (opt-in: TTTBase.linear_pipeline_parts).  Its MFMA scans continue from ANY step at both mini-batch sizes (the whole
+# state is fp32 in registers: ttt_hip_linear_forward_chunk, include/ttt_hip_parts.h), so where checkpoint groups are too few to cut
+# at - sampling: one group - the plan cuts at multiples of LIN_QUANTUM steps of the layer's mini-batch size instead: one 4 096-token
+# row block, the reasoning of CS16_QUANTUM above.  None = 4096 // CS; a number overrides (tests exercise the any-step cut at small size).
+LIN_QUANTUM = None
+
+
+def lin_quantum(CS: int) -> int:
+    return max(1, 4096 // CS) if LIN_QUANTUM is None else int(LIN_QUANTUM)
+
+
+# What the part loop of `prepass` needs to know about a scan kind: the name its result is injected under, the trailing shapes of the
+# state checkpoints ([B, NH, K, *shape]) at head_dim F, the layout in which the scan reads the [NH, F] LayerNorm parameters, and the
+# call that walks one part (the state tensors are replaced by the state after the part).
+class ScanKind:
+    def __init__(self, result, ck_shapes, ln_shape, chunk):
+        self.result, self.ck_shapes, self.ln_shape, self.chunk = result, ck_shapes, ln_shape, chunk
+
+
+MLP_SCAN = ScanKind("scan", lambda F: ((F, 4 * F), (1, 4 * F), (4 * F, F), (1, F)), lambda NH, F: (1, NH, 1, F),
+                    lambda ext, impl: ext.ttt_forward_chunk)
+LINEAR_SCAN = ScanKind("scan_lin", lambda F: ((F, F), (1, F)), lambda NH, F: (NH, F),
+                       lambda ext, impl: (lambda *a: ext.ttt_linear_forward_chunk(impl, *a)))
+
+
+def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n_pos, NH, state, last_eta, G, parts, kind=MLP_SCAN,
+            impl=None):
+    """Fills and returns {"linear3": (XQr, XKr, XVr), "scan": (out, W1c, b1c, W2c, b2c), "post": y, "wo": o} (no autograd).
+    ``kind=LINEAR_SCAN`` (``impl``: the kernel selector of HipLinear for this call): "linear3", "pre": (XQ, XK, XV) - the
+    pre-processed scan inputs, which FusedPre is a node of its own for -, "scan_lin": (out, W1c, b1c), "post", "wo"."""
     B, L, D = x.shape
     Fh = D // NH
     CS = last_eta.shape[-2]
@@ -178,9 +207,10 @@ def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n
         XQr, XKr, XVr, y, o = (e16(B, L, D) for _ in range(5))
         XQ, XK, XV = (e16(B, NH, L, Fh) for _ in range(3))
         out = e16(B, NH, NC, CS, Fh)
-        cks = (e32(B, NH, K, Fh, 4 * Fh), e32(B, NH, K, 1, 4 * Fh), e32(B, NH, K, 4 * Fh, Fh), e32(B, NH, K, 1, Fh))
+        cks = tuple(e32(B, NH, K, *shape) for shape in kind.ck_shapes(Fh))
         carry = [t.to(_F32).contiguous().clone() for t in state]          # the state entering the next part (the scan replaces it)
-        lw, lb = ln_w32.reshape(1, NH, 1, Fh), ln_b32.reshape(1, NH, 1, Fh)
+        lw, lb = ln_w32.reshape(kind.ln_shape(NH, Fh)), ln_b32.reshape(kind.ln_shape(NH, Fh))
+        scan_chunk = kind.chunk(ext, impl)
         pw32, pb32 = post_norm.weight.detach().to(_F32).contiguous(), post_norm.bias.detach().to(_F32).contiguous()
         mb = lambda t: t.view(B, NH, NC, CS, Fh)
         wts = [(m.weight.t(), m.bias, dst) for m, dst in ((wq, XQr), (wk, XKr), (wv, XVr))]
@@ -217,7 +247,7 @@ def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n
             side.wait_event(ready)
             with torch.cuda.stream(side):
                 s0, ns, _ = parts[c]
-                ext.ttt_forward_chunk(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, *carry, *cks, out, G, s0, ns)
+                scan_chunk(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, *carry, *cks, out, G, s0, ns)
                 ev = torch.cuda.Event()
                 ev.record(side)
             done.append(ev)
@@ -226,4 +256,7 @@ def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n
                 stage_out(c - 1)
         main.wait_event(done[-1])
         stage_out(len(parts) - 1)
-    return {"linear3": (XQr, XKr, XVr), "scan": (out, *cks), "post": y, "wo": o}
+    res = {"linear3": (XQr, XKr, XVr), kind.result: (out, *cks), "post": y, "wo": o}
+    if kind is LINEAR_SCAN:
+        res["pre"] = (XQ, XK, XV)
+    return res

@@ -145,6 +145,12 @@ class TTTBase(nn.Module):
         # and the last part's output projection, which grow with the sequence - at 63 s (343 groups) 8 parts measured 7 122 against 7 001
         # video-tok/s for 4 on one box (profiles/r5i_*); False: exactly `pipeline_parts`
         self.pipeline_parts_auto = True
+        # TTT-Linear forward as the same pipeline over (up to) this many parts: the MFMA scans of TTT-Linear continue from a state at
+        # any step (ttt_hip_linear_forward_chunk), at mini-batches of 16 and - with HipLinear.cs64_impl = "mfma" - of 64, with grad
+        # enabled too (the MFMA backwards read the checkpoints the parts wrote).  0 / 1 = off, the default: the layer in parts has not
+        # been measured against the layer in one piece on a training step yet (tools/ttt_layer_bench.py --ssm ttt_linear measures the
+        # forward alone); environment variable TTT_LINEAR_PIPELINE_PARTS.
+        self.linear_pipeline_parts = int(os.environ.get("TTT_LINEAR_PIPELINE_PARTS", "0"))
 
         D, NH, Fh = self.width, self.num_heads, self.head_dim
         self.wq = nn.Linear(D, NH * Fh, bias=True)
@@ -380,22 +386,27 @@ class TTTBase(nn.Module):
         import test_time_training as ext
         from ttt_amd.models.ssm import pipeline
         with torch.no_grad():
-            st = [self._per_batch(p, B) for p in (self.W1, self.b1, self.W2, self.b2)]
+            mlp = isinstance(self, TTTMLP)
+            st = [self._per_batch(p, B) for p in ((self.W1, self.b1, self.W2, self.b2) if mlp else (self.W1, self.b1))]
             last_eta = eta.detach().to(torch.bfloat16)[:, :, :, -1, :, None].contiguous()
             w32 = self.ttt_norm_weight.detach().to(torch.float32).contiguous()
             b32 = self.ttt_norm_bias.detach().to(torch.float32).contiguous()
+            kind = dict(kind=pipeline.MLP_SCAN) if mlp else \
+                dict(kind=pipeline.LINEAR_SCAN, impl=HipLinear._impl(self.mini_batch_size, self.head_dim, torch.bfloat16))
             res = pipeline.prepass(ext, x.detach(), self.wq, self.wk, self.wv, self.wo, self.post_norm, w32, b32, rope, src, pos,
                                    getattr(pos, "_ttt_max_pos", None), self.num_heads, st, last_eta,
-                                   self._group_size(L // self.mini_batch_size), parts)
+                                   self._group_size(L // self.mini_batch_size), parts, **kind)
         with pipeline.injecting(res):
             return self._fused_nodes(x, rope, src, pos, eta, heads_only, piped=True)
 
     def _pipeline_plan(self, x, meta, L, reverse, heads_only):
         """the parts of a pipelined forward, or None when this call runs as one piece: not TTT-MLP on the MFMA scan at mini-batches of
         64 or (forward only, under ``no_grad``) of 16, a scan too short to cut, a head shard, a re-materialisation that gets its scan
-        result handed back"""
+        result handed back.  A TTT-Linear layer has a plan of its own, opt-in (``_linear_pipeline_plan``)."""
         from ttt_amd.infra import remat_cache
         from ttt_amd.models.ssm import pipeline
+        if isinstance(self, TTTLinear):
+            return self._linear_pipeline_plan(x, meta, L, reverse, heads_only)
         n = self.pipeline_parts
         CS = self.mini_batch_size
         if n < 2 or heads_only or not isinstance(self, TTTMLP) or CS not in (64, 16) or remat_cache.replaying("scan"):
@@ -425,6 +436,11 @@ class TTTBase(nn.Module):
         import test_time_training as ext
         if ext.resolved_impl(x.shape[0], self.num_heads, NC, CS, self.head_dim, G, torch.bfloat16, mlp=True, backward=False) != "mfma":
             return None
+        return self._planned_parts(meta, L, reverse, CS, unit, n)
+
+    def _planned_parts(self, meta, L, reverse, CS, unit, n):
+        """``pipeline.plan_parts`` of ``n`` parts of whole ``unit``s of steps over this call's scan order, cached"""
+        from ttt_amd.models.ssm import pipeline
         key = ("parts", n, unit, meta.num_chunks, meta.text_length, meta.seq_text_length, meta.init_offset, meta.base_offset, L, reverse)
         hit = self._perm_cache.get(key)
         if hit is None:
@@ -434,6 +450,31 @@ class TTTBase(nn.Module):
                 seq = r if seq is None else r[seq]                                 # -> token of the input sequence (= the maps' src)
             hit = self._perm_cache[key] = pipeline.plan_parts(seq, L, CS, unit, n)
         return hit
+
+    def _linear_pipeline_plan(self, x, meta, L, reverse, heads_only):
+        """the plan of a TTT-Linear layer: ``linear_pipeline_parts`` parts (opt-in) wherever HipLinear would run this call on the MFMA
+        scan - mini-batches of 16, or of 64 with ``HipLinear.cs64_impl = "mfma"`` -, with or without grad.  Parts are whole checkpoint
+        groups when there are at least two per part, multiples of ``pipeline.lin_quantum`` steps otherwise (the scan continues from any
+        step; sampling has one group); at least two such units per part on average, or the layer stays one piece."""
+        from ttt_amd.infra import remat_cache
+        from ttt_amd.models.ssm import pipeline
+        n = self.linear_pipeline_parts
+        CS = self.mini_batch_size
+        if n < 2 or heads_only or remat_cache.replaying("scan"):
+            return None
+        if not linear3_applies(self.wq, self.wk, self.wv, x) or not linear3_applies(self.wo, self.wo, self.wo, x):
+            return None
+        NC = L // CS
+        G = self._group_size(NC)
+        unit = G if -(-NC // G) >= 2 * n else pipeline.lin_quantum(CS)
+        n = min(n, -(-NC // unit) // 2)
+        if n < 2:
+            return None
+        import test_time_training as ext
+        impl = HipLinear._impl(CS, self.head_dim, torch.bfloat16)
+        if ext.resolved_impl(x.shape[0], self.num_heads, NC, CS, self.head_dim, G, torch.bfloat16, mlp=False, backward=False, impl=impl) != "mfma":
+            return None
+        return self._planned_parts(meta, L, reverse, CS, unit, n)
 
     def _eta_rows(self, x, rev, meta, L):
         """eta (tiny: [B, L, NH]): per-token learning rate in the order of the (reversed) sequence, then the reference's tile
@@ -470,7 +511,8 @@ class TTTBase(nn.Module):
             out.index_copy_(1, src.long(), Y.reshape(B, NH, L, Fh).transpose(1, 2))
             return out.view(B, L, NH * Fh)
         y = FusedPost.apply(Y.reshape(B, NH, L, Fh), self.post_norm.weight, self.post_norm.bias, src, self.post_norm.eps)
-        if self.pipeline_parts >= 2 and isinstance(self, TTTMLP) and linear3_applies(self.wo, self.wo, self.wo, y):
+        may_pipe = self.pipeline_parts >= 2 if isinstance(self, TTTMLP) else self.linear_pipeline_parts >= 2
+        if may_pipe and linear3_applies(self.wo, self.wo, self.wo, y):
             # the output projection as a node of our own whenever this layer MAY run pipelined - also in the calls that do not (a
             # re-materialisation that gets its scan result handed back): torch's checkpoint wants the recomputation to save what
             # the forward pass saved, node for node; the node takes the pre-pass's result when there is one

@@ -41,7 +41,8 @@ def ttt_linear_forward(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, XQW, 
 
 def ttt_linear_backward(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, uW1, ub1, gout, W1g, b1g, dlnw, dlnb, dW1, db1,
                         deta, dQ, dK, dV, G):
-    g = O.linear_backward(_f(XQ), _f(XK), _f(XV), _f(last_eta), _f(ln_w), _f(ln_b), (_f(W1c), _f(b1c)), G, _f(gout))
+    g = O.linear_backward(_f(XQ), _f(XK), _f(XV), _f(last_eta), _f(ln_w), _f(ln_b), (_f(W1c), _f(b1c)), G, _f(gout),
+                          dst_last=(_f(uW1), _f(ub1)))
     for dst, k in ((dlnw, "dln_w"), (dlnb, "dln_b"), (dW1, "dW1"), (db1, "db1"), (deta, "dlast_eta"), (dQ, "dXQ"),
                    (dK, "dXK"), (dV, "dXV")):
         dst.copy_(g[k])

@@ -422,12 +422,14 @@ def _lin_step_bwd(st_in, Q, K, V, eta, gam, bet, eps, dOut, dst):
     return (dW1, db1), dQ, dK, dV, deta, dgam, dbet
 
 
-def linear_backward(XQ, XK, XV, last_eta, ln_w, ln_b, cks, G: int, dXQW, eps: float = LN_EPS):
+def linear_backward(XQ, XK, XV, last_eta, ln_w, ln_b, cks, G: int, dXQW, dst_last=None, eps: float = LN_EPS):
+    """TTT-Linear backward with the kernel contract; ``dst_last`` = (dW1, db1) [B,NH,...] flowing in from after the last step
+    (None: zeros), as ``mlp_backward`` has it."""
     B, NH, NC, CS, Fd = XQ.shape
     gam = ln_w.reshape(1, NH, 1, Fd)
     bet = ln_b.reshape(1, NH, 1, Fd)
     W1c, b1c = cks
-    dst = (torch.zeros_like(W1c[:, :, 0]), torch.zeros_like(b1c[:, :, 0]))
+    dst = (torch.zeros_like(W1c[:, :, 0]), torch.zeros_like(b1c[:, :, 0])) if dst_last is None else tuple(dst_last)
     dQ = torch.zeros_like(XQ); dK = torch.zeros_like(XQ); dV = torch.zeros_like(XQ)
     deta = torch.zeros_like(last_eta)
     dgam = torch.zeros(B, NH, 1, Fd, dtype=XQ.dtype)
@@ -547,3 +549,61 @@ def lin_step_rounded(W1, b1, Q, K, V, eta, gam, bet, eps=LN_EPS, on=LIN_ROUND):
     if not on:
         return _lin_step_primal(W1, b1, Q, K, V, eta, gam, bet, eps)[:2]
     return _lin_step_scaled(W1, b1, Q, K, V, eta, gam, bet, eps, frozenset(on))
+
+
+# --------------------------------------------------------------------------- rounding model of the MFMA TTT-Linear sweeps
+# One reverse step in fp64 with a bf16 rounding at every point where lin16::backward (csrc/ttt_lin16_body.h) and lin64::backward
+# (csrc/ttt_lin64_body.h) round - both bodies round at the same points, so one set serves both:
+#   "W"     the packed copies of W1 and W1n (the scratch slots / L_WHI) in every product that reads them: Z1, Z1b, dQ, dK
+#   "Gs"    Gs = -eta gZ1 of the re-run forward step: operand of the W1n update, and b1n sums the ROUNDED Gs (ones-MFMA)
+#   "dZ1b"  the packed dZ1b: operand of the dW1n update and of dQ
+#   "dW1n"  the packed dW1n (after its update): operand of K dW1n in dgZ1 and of A1 = gZ1 dW1n^T
+#   "gZ1"   the packed gZ1 in A1 (d eta's gZ1 . db1n term and the LayerNorm double-backward read the fp32 gZ1)
+#   "dZ1"   the packed dZ1: operand of dK and of the dW1 update
+#   "out"   the bf16 stores of dXQ, dXK, dXV and d eta
+# The db1 sums (colsum16 of the fp32 tiles) and the fp32 accumulators dW1 / db1 / dln_w / dln_b stay unrounded.
+LIN_BWD_ROUND_POINTS = ("W", "Gs", "dZ1b", "dW1n", "gZ1", "dZ1", "out")
+LIN_BWD_ROUND = frozenset(LIN_BWD_ROUND_POINTS)
+
+
+def _lin_step_bwd_scaled(st_in, Q, K, V, eta, gam, bet, dOut, dst, eps, on):
+    r = lambda name, x: _bf(x) if name in on else x
+    T = lambda x: x.transpose(-1, -2)
+    W1, b1 = st_in
+    Fd = Q.shape[-1]
+    W1o = r("W", W1)
+    xh, std = _ln_stats(K @ W1o + b1, eps)
+    go = gam * xh + bet - (V - K)
+    gxh = go * gam
+    gZ1 = (Fd * gxh - gxh.sum(-1, keepdim=True) - xh * (gxh * xh).sum(-1, keepdim=True)) / (Fd * std)
+    Gs = r("Gs", -eta * gZ1)
+    W1n = r("W", W1 + T(K) @ Gs)
+    b1n = b1 + Gs.sum(-2, keepdim=True)
+    xhl, stdl = _ln_stats(Q @ W1n + b1n, eps)
+    dW1n, db1n = dst
+    dgam = (dOut * xhl).sum(-2, keepdim=True)
+    dbet = dOut.sum(-2, keepdim=True)
+    dZ1b = _ln_bwd(dOut, xhl, stdl, gam, Fd)
+    dZ1bo = r("dZ1b", dZ1b)
+    dW1n = dW1n + T(Q) @ dZ1bo
+    db1n = db1n + dZ1b.sum(-2, keepdim=True)
+    dQ = dOut + dZ1bo @ T(W1n)
+    dW1no = r("dW1n", dW1n)
+    A1 = r("gZ1", gZ1) @ T(dW1no)
+    dgZ1 = -eta * (K @ dW1no + db1n)
+    deta = -(K * A1).sum(-1, keepdim=True) - (gZ1 * db1n).sum(-1, keepdim=True)
+    dZ1, dgam2, dbet2, dt = _ln_l2_bwd_bwd(dgZ1, xh, std, go, gxh, gZ1, gam, Fd)
+    dZ1o = r("dZ1", dZ1)
+    dK = -eta * A1 - dt + dZ1o @ T(W1o)
+    dW1 = dW1n + T(K) @ dZ1o
+    db1 = db1n + dZ1.sum(-2, keepdim=True)
+    return ((dW1, db1), r("out", dQ), r("out", dK), r("out", dt), r("out", deta),
+            dgam + dgam2.sum(-2, keepdim=True), dbet + dbet2.sum(-2, keepdim=True))
+
+
+def lin_step_bwd_rounded(st_in, Q, K, V, eta, gam, bet, dOut, dst, eps=LN_EPS, on=LIN_BWD_ROUND):
+    """``_lin_step_bwd`` with the roundings named in ``on`` -> ((dW1, db1), dQ, dK, dV, deta, dgam, dbet).  With no point switched
+    on it IS ``_lin_step_bwd``."""
+    if not on:
+        return _lin_step_bwd(st_in, Q, K, V, eta, gam, bet, eps, dOut, dst)
+    return _lin_step_bwd_scaled(st_in, Q, K, V, eta, gam, bet, dOut, dst, eps, frozenset(on))

@@ -120,6 +120,40 @@ SCAN_TOL_GENERIC = dict(SCAN_TOL, delta=1e-4, delta_block=1e-4, row=5e-3, ulp_fr
 SCAN_MEASURED = {"delta": 0.00353, "delta_block": 0.00616, "row": 0.00508, "ulp_frac": 0.0928, "ulp_max": 13.3, "gain": 0.000548}
 SCAN_MEASURED_GENERIC = {"delta": 1.36e-05, "delta_block": 1.45e-05, "row": 0.00111, "ulp_frac": 0.0, "ulp_max": 0.5, "gain": 0.000339}
 
+# Tolerances of ONE CALL of the TTT-Linear backward sweeps (one step, or one group: a G-step horizon) against oracle/ttt_oracle.py
+# from the same checkpoint and the same nonzero upstream state gradient (tests/scan_bwd_cases.py: the metrics;
+# tests/test_scan_bwd_oracle_gpu.py), fixed by the sensitivity table of tests/test_scan_bwd_oracle_cpu.py BEFORE the device ran (the
+# device column was filled in afterwards: the kernels round where the model rounds and land on its values to three digits):
+# each >= 2x the oracle's rounding model (O.lin_step_bwd_rounded, worst over the cases of the GPU file), each <= 1/3 of the nearest
+# mutation its metric must catch (the minimum over mini-batches of 16 and 64, base and high learning rate).
+#   metric        rounding model   MI355X    threshold   nearest must-catch mutation (its distance)
+#   dstate        2.6e-3           2.6e-3    1e-2        last token left out of the dW1 / db1 update (1.5e-1)
+#   dstate_block  3.0e-3           3.0e-3    1.2e-2      increment x 1.05 in one 16-column block (5.0e-2)
+#   row           5.4e-3           5.4e-3    2e-2        Q of step i + 1 (1.2e-1); dK without -eta A1 (2.0e-1); dW1_last left out (2.0e-1)
+#   deta          2.7e-3           2.7e-3    1e-2        the gZ1 . db1n term dropped (1.0)
+#   dln           1.7e-3           1.7e-3    5e-3        the inner LayerNorm's share dropped (1.0)
+#   gain          7.6e-4           7.6e-4    2.5e-3      unbiased variance in the output LayerNorm (8.0e-3)
+# Reported only: LayerNorm epsilon 1e-6 (dstate 1.5e-2 .. 1.7e-2, row 1.7e-2 .. 2.0e-2): separating it would take a threshold under
+# 5e-3, which is under 2x the rounding model.  The unbiased output variance is caught by gain alone (row 1.0e-2 .. 1.4e-2).
+SCAN_BWD_TOL = {
+    "dstate": 1e-2,         # worst rel-L2 per (b, h) of the increments dW1 - dW1_last, db1 - db1_last
+    "dstate_block": 1.2e-2, # the same of one 16-column block of the increment
+    "row": 2e-2,            # worst rel-L2 of one (b, h, step, token) row of dXQ, dXK, dXV against the bf16-rounded oracle
+    "deta": 1e-2,           # worst rel-L2 per (b, h, step) of d eta
+    "dln": 5e-3,            # worst rel-L2 per (b, h) of dln_w, dln_b
+    "gain": 2.5e-3,         # worst |least-squares gain - 1| of dXQ - dOut of one (b, h, step)
+}
+# The generic kernel: fp32 arithmetic, only the stores of dXQ, dXK, dXV, d eta round (to bf16; nothing with fp32 activations).  Its
+# reference-alone level is the oracle's step in fp32 arithmetic (dstate 7.2e-7, dstate_block 7.9e-7, dln 1.7e-7: fp32 sums of 16 .. 64
+# terms; with the bf16 stores row 1.6e-3, d eta 2.1e-3 - one bf16 rounding per element bounds both by 2^-8 = 3.9e-3 -, gain 1.5e-4).
+# dln is also the bound on the fp32 add order when dln_w / dln_b of a call are summed from the partials of its one-group calls.
+SCAN_BWD_TOL_GENERIC = dict(SCAN_BWD_TOL, dstate=2e-5, dstate_block=2e-5, row=5e-3, deta=5e-3, dln=1e-5, gain=1e-3)
+# the kernels' worst values on an MI355X over the cases of test_scan_bwd_oracle_gpu.py (profiles/r14_scan_bwd_oracle_gpu.log)
+# (a call over K groups against the chain of its one-group calls: equal bits on all three kernels; dln_w / dln_b within 1.2e-7 of the
+# sum of the partials)
+SCAN_BWD_MEASURED = {"dstate": 0.00255, "dstate_block": 0.00297, "row": 0.00541, "deta": 0.00265, "dln": 0.00168, "gain": 0.000759}
+SCAN_BWD_MEASURED_GENERIC = {"dstate": 7.51e-07, "dstate_block": 8.2e-07, "row": 0.000911, "deta": 0.00213, "dln": 1.81e-07, "gain": 0.000153}
+
 
 def scene_meta(text_length, num_chunks, num_frames, H, W):
     """SequenceMetadata of ``num_chunks`` scenes of ``text_length`` text tokens over ``num_frames`` H x W latent frames"""

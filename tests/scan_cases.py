@@ -296,7 +296,7 @@ def build_emul(name):
     os.makedirs(build, exist_ok=True)
     so = os.path.join(build, f"lib{name}.so")
     srcs = [os.path.join(here, "emul", f) for f in (name + ".cpp", "wave_emul.h")] + \
-           [os.path.join(csrc, f) for f in ("ttt_lin16_body.h", "ttt_mlp16_body.h", "ttt_wave_types.h")]
+           [os.path.join(csrc, f) for f in ("ttt_lin16_body.h", "ttt_lin64_body.h", "ttt_mlp16_body.h", "ttt_wave_types.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call([CLANG, "-std=c++20", "-O1", "-pthread", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-Wno-psabi",
                                "-I", csrc, "-I", os.path.join(here, "emul"), srcs[0], "-o", so])

@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "../../include/ttt_hip_parts.h"
+#include "../../include/ttt_hip_bwd_parts.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -255,6 +256,48 @@ int ttt_hip_linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, voi
     if (r == TTT_IMPL_MFMA) ttt::mfma::linear_backward(d, a, ws, (hipStream_t)stream);
     else ttt::generic::linear_backward(d, a, ws, (hipStream_t)stream);
     return post_launch("linear_backward");
+}
+
+// include/ttt_hip_bwd_parts.h
+static int check_bwd_parts(const char* fmt_what, const ttt_dims* d, int k0, int nk, const void* slots, size_t slots_bytes) {
+    // (fp32 activations, TTT_IMPL_GENERIC and mini-batches of 64 under TTT_IMPL_AUTO resolve to the generic kernels)
+    if (resolve(d, false, true) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
+        return fail("ttt_hip: %s: only the MFMA sweep (mini-batches of 16; of 64 on an explicit TTT_IMPL_MFMA) runs over a range of checkpoint groups", fmt_what);
+    const int K = (d->NC + d->G - 1) / d->G;
+    if (k0 < 0 || nk <= 0 || k0 > K - nk) return fail("ttt_hip: %s: the groups [k0, k0 + nk) must lie inside [0, K)", fmt_what);
+    if (!slots || slots_bytes < ttt::mfma::linear_backward_parts_slots(d, nk))
+        return fail("ttt_hip: %s: slot workspace null or smaller than ttt_hip_linear_backward_parts_slots(d, nk)", fmt_what);
+    return 0;
+}
+size_t ttt_hip_linear_backward_parts_slots(const ttt_dims* d, int nk) {
+    if (check_dims(d) || nk <= 0) return 0;
+    return ttt::mfma::linear_backward_parts_slots(d, nk);
+}
+size_t ttt_hip_linear_backward_parts_carry(const ttt_dims* d) {
+    if (check_dims(d)) return 0;
+    return ttt::mfma::linear_backward_parts_carry(d);
+}
+int ttt_hip_linear_recompute_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, void* slots, size_t slots_bytes,
+                                    void* stream) {
+    if (check_dims(d)) return -1;
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias); NEED(W1_checkpoints); NEED(b1_checkpoints);
+    if (check_bwd_parts("linear_recompute_groups", d, k0, nk, slots, slots_bytes)) return -1;
+    ttt::mfma::linear_recompute_groups(d, a, k0, nk, slots, (hipStream_t)stream);
+    return post_launch("linear_recompute_groups");
+}
+int ttt_hip_linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
+                                float* ln_carry, size_t carry_bytes, void* stream) {
+    if (check_dims(d)) return -1;
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_XQW); NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias);
+    NEED(grad_L_W1_init); NEED(grad_L_b1_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
+    if (check_bwd_parts("linear_sweep_groups", d, k0, nk, slots, slots_bytes)) return -1;
+    if (!ln_carry || carry_bytes < ttt::mfma::linear_backward_parts_carry(d))
+        return fail("ttt_hip: linear_sweep_groups: ln_carry null or smaller than ttt_hip_linear_backward_parts_carry(d)");
+    ttt::mfma::linear_sweep_groups(d, a, k0, nk, slots, ln_carry, (hipStream_t)stream);
+    return post_launch("linear_sweep_groups");
 }
 
 /* ---- fused pre / post-processing of the TTT layer (ttt_prepost.hip) --------------------------------- */

@@ -56,6 +56,21 @@ TTT_WV_FN bf16x8 stack(f32x4 a, f32x4 b) {
     bf16x8 r = {(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
     return r;
 }
+// a * b + c as ONE fused multiply-add, fixed in the source.  For the sums of two products in the reverse step of the backward in
+// parts: left to the compiler, which of the two products is fused into the add depends on the code around the expression, and the
+// part kernels have to round as the one-call kernels do (tests/test_linear_bwd_parts_gpu.py compares the bits).  The other product is
+// passed as `c`, rounded.  (The emulator's host arithmetic fuses nothing, in backward() as here.)
+TTT_WV_FN f32x4 fma4(f32x4 a, f32x4 b, f32x4 c) {
+#ifdef __HIP_DEVICE_COMPILE__
+    f32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = __builtin_fmaf(a[e], b[e], c[e]);
+    return r;
+#else
+    return a * b + c;
+#endif
+}
+TTT_WV_FN f32x4 splat4(float v) { f32x4 r = {v, v, v, v}; return r; }
 TTT_WV_FN bf16x8 cat(bf16x4 lo, bf16x4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
 
 // rho-order operand (lane = this lane's row i of the tile, k = columns c0 .. c0 + 31) of a row-major [16][TS] LDS tile
@@ -364,6 +379,296 @@ TTT_WV_FN void transposed_packs(BK& bk, const f32x4 (&T)[4][4], bf16x8 (&out)[2]
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int fa = 0; fa < 4; ++fa) out[ks][fa] = cat(tr4(bk, L_TR, TRS, 32 * ks, 16 * fa), tr4(bk, L_TR, TRS, 32 * ks + 16, 16 * fa));
+}
+
+// ---- the pieces of the backward in parts (recompute_groups / sweep_groups, behind backward() below): the state loads, the recompute
+// step and the reverse step of backward() as functions.  backward() itself keeps its steps inline: moving them into these functions
+// was tried and changed which products its compiled code fuses into multiply-adds, i.e. the bits of an existing kernel.  The
+// arithmetic here is backward()'s, statement by statement; where the source leaves the compiler a choice of fused product (sums of
+// two products), fma4 fixes the one backward()'s compiled code takes, so that the parts round as the one call does. --------------
+static_assert(LIN_PART_SLOT_BYTES == SLOT_BYTES + 64 * sizeof(float), "a slot of the backward in parts: packed state + bias row");
+
+struct BwdConsts {
+    float gam[4], bet[4];
+    bf16x4 ONES, IDP, IDN;    // ones / +-identity as mma16 A operand (lane = t = i, k-slot e = token 4g + e)
+    float eps;
+};
+// what a sweep carries from step to step
+struct BwdCarry {
+    f32x4 dWt[4][4];      // [fa][fb]  dW1[16fa + 4g + r][16fb + i]    (rows = f_in, lane = f_out)
+    float db[4];          // db1[16fb + i]
+    float dgam[4], dbet[4];     // per-lane partial sums over this lane's token rows
+};
+template <class BK>
+TTT_WV_FN void bwd_consts(BK& bk, const Lin16Params& p, int head, BwdConsts& c) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        c.gam[fb] = p.ln_w[(size_t)head * 64 + 16 * fb + i];
+        c.bet[fb] = p.ln_b[(size_t)head * 64 + 16 * fb + i];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        c.ONES[e] = (__bf16)1.0f;
+        c.IDP[e] = (__bf16)((4 * g + e) == i ? 1.0f : 0.0f);
+        c.IDN[e] = (__bf16)((4 * g + e) == i ? -1.0f : 0.0f);
+    }
+    c.eps = p.eps;
+}
+// a [64][64] fp32 matrix in global memory <-> tiles T[fa][fb] (rows = f_in, lane = f_out) ; a [64] row <-> v[fb] (lane = f)
+template <class BK>
+TTT_WV_FN void load_matrix(BK& bk, const float* M, f32x4 (&T)[4][4]) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) T[fa][fb][r] = M[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * fb + i];
+}
+template <class BK>
+TTT_WV_FN void store_matrix(BK& bk, float* M, const f32x4 (&T)[4][4]) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) M[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * fb + i] = T[fa][fb][r];
+}
+template <class BK>
+TTT_WV_FN void load_row(BK& bk, const float* v, float (&o)[4]) {
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) o[fb] = v[16 * fb + (bk.lane() & 15)];
+}
+// parks the state W1t as packed operands in both orientations at `slot` ; WF: the packs the forward step takes
+template <class BK>
+TTT_WV_FN void park_state(BK& bk, const f32x4 (&W1t)[4][4], char* slot, bf16x8 (&WF)[2][4]) {
+    bf16x8 WT[2][4];
+    transposed_packs(bk, W1t, WT);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            WF[ks][f] = stack(W1t[2 * ks][f], W1t[2 * ks + 1][f]);
+            st_pack(bk, slot, ks * 4 + f, WF[ks][f]);
+            st_pack(bk, slot, 8 + ks * 4 + f, WT[ks][f]);
+        }
+}
+// one recomputed step (same arithmetic as forward_part): K, V tiles at Kt, Vt, eta at eta_off, WF the packed entering state ;
+// W1t, b1v: the state entering the step -> the state after it.  `l`: the lane index the step loop made opaque.
+template <class BK>
+TTT_WV_FN void recompute_step(BK& bk, int l, const BwdConsts& c, int Kt, int Vt, int eta_off, const bf16x8 (&WF)[2][4],
+                              f32x4 (&W1t)[4][4], float (&b1v)[4]) {
+    const int g = l >> 4;
+    const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
+    const f32x4 eta4 = bk.template lds<f32x4>(eta_off + 4 * g * 4);
+    bf16x4 kT[4];
+    f32x4 z[4], tg[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        kT[fb] = tr4(bk, Kt, TS, 0, 16 * fb);
+        f32x4 a = zero4();
+        a = bk.mma32(kA0, WF[0][fb], a);
+        a = bk.mma32(kA1, WF[1][fb], a);
+        z[fb] = a + b1v[fb];
+        tg[fb] = bk.mma16(c.IDN, kT[fb], bk.mma16(c.IDP, tr4(bk, Vt, TS, 0, 16 * fb), zero4()));
+    }
+    bf16x4 gzp[4];
+    {
+        InnerGrad ig;
+        inner_grad(bk, z, tg, c.gam, c.bet, c.eps, ig);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) gzp[fb] = pack4(ig.gz[fb] * (-eta4));
+    }
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        b1v[fb] += bk.mma16(c.ONES, gzp[fb], zero4())[0];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) W1t[fa][fb] = bk.mma16(kT[fa], gzp[fb], W1t[fa][fb]);
+    }
+}
+// one step of the reverse walk.  Tiles of the step at Kt, Vt, Qt, Dt, eta at eta_off ; slot / b1v: the state entering the step,
+// slot_n / b1n: the state after it ; y: the carried gradients, entering as those of the state after the step, leaving as those of
+// the state entering it ; deta, dXQ, dXK, dXV of the step go to tile `tile` of the whole sequence.  `mid()` runs between the outer
+// LayerNorm backward and the inner step: where the caller parks the tiles it requested for the next step into the buffers this
+// step does not use.  Ends with the carried update (10); the caller fences LDS behind it.
+template <class BK, class Mid>
+TTT_WV_FN void reverse_step(BK& bk, int l, const Lin16Params& p, const BwdConsts& c, BwdCarry& y, size_t tile, int Kt, int Vt, int Qt,
+                            int Dt, int eta_off, const char* slot, const char* slot_n, const float (&b1v)[4], const float (&b1n)[4],
+                            Mid&& mid) {
+    const int g = l >> 4, i = l & 15;
+    const f32x4 eta4 = bk.template lds<f32x4>(eta_off + 4 * g * 4);
+    // ---- (2) outer LayerNorm backward: Z1b = Q W1n + b1n ; dZ1b -----------------------------------------------------------
+    bf16x4 qT[4], dZbp[4];
+    f32x4 dq[4];                     // starts as dOut (accumulator layout), becomes dQ
+    {
+        const bf16x8 qA0 = rho_read(bk, Qt, 0), qA1 = rho_read(bk, Qt, 32);
+        f32x4 yy[4], dxl[4], t2[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            qT[fb] = tr4(bk, Qt, TS, 0, 16 * fb);
+            f32x4 a = zero4();
+            a = bk.mma32(qA0, ld_pack(bk, slot_n, fb), a);
+            a = bk.mma32(qA1, ld_pack(bk, slot_n, 4 + fb), a);
+            yy[fb] = a + b1n[fb];
+            dq[fb] = bk.mma16(c.IDP, tr4(bk, Dt, TS, 0, 16 * fb), zero4());                     // exact dOut
+        }
+        const f32x4 rstdl = normalize_rows(bk, yy, c.eps);                                    // yy <- x_hat of the output LN
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dx = dq[fb] * yy[fb];
+            y.dgam[fb] += dx[0] + dx[1] + dx[2] + dx[3];
+            y.dbet[fb] += dq[fb][0] + dq[fb][1] + dq[fb][2] + dq[fb][3];
+            dxl[fb] = dq[fb] * c.gam[fb];
+            t2[fb] = dxl[fb] * yy[fb];
+        }
+        const f32x4 u1 = rowsum64(bk, dxl), u2 = rowsum64(bk, t2);
+        const f32x4 sc = rstdl * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dzb = (64.0f * dxl[fb] - u1 - yy[fb] * u2) * sc;
+            dZbp[fb] = pack4(dzb);
+            y.db[fb] += colsum16(bk, dzb);                                                      // db1n += colsum dZ1b (fp32)
+        }
+    }
+    // ---- (3) dW1n += Q^T dZ1b ; db1n += colsum dZ1b ------------------------------------------------------------------------------
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) y.dWt[fa][fb] = bk.mma16(qT[fa], dZbp[fb], y.dWt[fa][fb]);
+    }
+    // ---- (4) dQ = dOut + dZ1b W1n^T ------------------------------------------------------------------------------------------------
+    {
+        bf16x8 aZ[2];
+        image_of(bk, L_IMG, dZbp, aZ);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dq[fa] = bk.mma32(aZ[0], ld_pack(bk, slot_n, 8 + fa), dq[fa]);
+            dq[fa] = bk.mma32(aZ[1], ld_pack(bk, slot_n, 12 + fa), dq[fa]);
+        }
+        store_rows(bk, L_IMG + IMG_BYTES, dq, p.dXQ + tile * 1024);
+    }
+    mid();
+    bk.lds_fence();
+    // ---- (1) inner forward of the step: Z1 = K W + b, LN / L2 gradient ------------------------------------------------
+    const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
+    bf16x4 kT[4];
+    InnerGrad ig;
+    {
+        f32x4 z[4], tg[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            kT[fb] = tr4(bk, Kt, TS, 0, 16 * fb);
+            f32x4 a = zero4();
+            a = bk.mma32(kA0, ld_pack(bk, slot, fb), a);
+            a = bk.mma32(kA1, ld_pack(bk, slot, 4 + fb), a);
+            z[fb] = a + b1v[fb];
+            tg[fb] = bk.mma16(c.IDN, kT[fb], bk.mma16(c.IDP, tr4(bk, Vt, TS, 0, 16 * fb), zero4()));   // exact V - K
+        }
+        inner_grad(bk, z, tg, c.gam, c.bet, c.eps, ig);
+    }
+    bk.lds_fence();
+    // ---- (6) dgZ1 = -eta (K dW1n + db1n) ; (8) backward of the fused LN / L2 gradient -> dZ1, dt, dgamma, dbeta -----------------
+    bf16x4 dZ1p[4];
+    float dbz[4];                        // colsum dZ1 (fp32), added to db1 in (10) - d(eta) in (7) needs db1n
+    f32x4 dk[4];                     // starts as -dt (dt = gradient w.r.t. the target V - K = dV)
+    {
+        f32x4 dgz[4], mGr[4], t2[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            f32x4 a = zero4();
+            a = bk.mma32(kA0, stack(y.dWt[0][fb], y.dWt[1][fb]), a);
+            a = bk.mma32(kA1, stack(y.dWt[2][fb], y.dWt[3][fb]), a);
+            dgz[fb] = (a + y.db[fb]) * (-eta4);
+            mGr[fb] = dgz[fb] * (-ig.rstd);
+            t2[fb] = mGr[fb] * ig.xh[fb];
+        }
+        const f32x4 s1 = rowsum64(bk, mGr) * (1.0f / 64.0f), s2 = rowsum64(bk, t2) * (1.0f / 64.0f);
+        const f32x4 c2 = ig.s2g * (1.0f / 64.0f);
+        f32x4 dxh[4], dstd[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dgxh = fma4(dgz[fb], ig.rstd, s1) + ig.xh[fb] * s2;
+            const f32x4 dy = dgxh * c.gam[fb];
+            const f32x4 dg = fma4(ig.go[fb], dgxh, dy * ig.xh[fb]);
+            y.dgam[fb] += dg[0] + dg[1] + dg[2] + dg[3];
+            y.dbet[fb] += dy[0] + dy[1] + dy[2] + dy[3];
+            dk[fb] = dy;                                                                       // = -dt
+            dxh[fb] = fma4(ig.go[fb] * c.gam[fb], s2, dy * c.gam[fb]) + mGr[fb] * c2;
+            dstd[fb] = fma4(dgz[fb], ig.gz[fb], dxh[fb] * ig.xh[fb]) * (-ig.rstd);
+        }
+        const f32x4 v1 = rowsum64(bk, dxh) * (1.0f / 64.0f), v2 = rowsum64(bk, dstd) * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dz1 = fma4(dxh[fb] - v1, ig.rstd, ig.xh[fb] * v2);
+            dZ1p[fb] = pack4(dz1);
+            dbz[fb] = colsum16(bk, dz1);
+        }
+        f32x4 dv[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) dv[fb] = -dk[fb];
+        store_rows(bk, L_IMG + IMG_BYTES, dv, p.dXV + tile * 1024);                              // dV = dt
+    }
+    bk.lds_fence();
+    // ---- (5, 7, 9) A1 = gZ1 dW1n^T ; d eta ; dK = -eta A1 - dt + dZ1 W^T --------------------------------------------------------------
+    {
+        bf16x8 dWT[2][4];
+        transposed_packs(bk, y.dWt, dWT);
+        bf16x4 gzq[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) gzq[fb] = pack4(ig.gz[fb]);
+        bf16x8 aG[2];
+        image_of(bk, L_IMG, gzq, aG);
+        f32x4 acc[4];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            f32x4 a1 = zero4();
+            a1 = bk.mma32(aG[0], dWT[0][fa], a1);
+            a1 = bk.mma32(aG[1], dWT[1][fa], a1);
+            dk[fa] -= a1 * eta4;
+            const f32x4 kc = bk.mma16(c.IDP, kT[fa], zero4());                                  // exact K, accumulator layout
+            acc[fa] = fma4(ig.gz[fa], splat4(y.db[fa]), kc * a1);
+        }
+        const f32x4 de = rowsum64(bk, acc);
+        if (i == 0) *reinterpret_cast<bf16x4*>(p.deta + tile * 16 + 4 * g) = pack4(-de);
+    }
+    bk.lds_fence();
+    {
+        bf16x8 aD[2];
+        image_of(bk, L_IMG, dZ1p, aD);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dk[fa] = bk.mma32(aD[0], ld_pack(bk, slot, 8 + fa), dk[fa]);
+            dk[fa] = bk.mma32(aD[1], ld_pack(bk, slot, 12 + fa), dk[fa]);
+        }
+        store_rows(bk, L_IMG + IMG_BYTES, dk, p.dXK + tile * 1024);
+    }
+    // ---- (10) dW1 = dW1n + K^T dZ1 ; db1 = db1n + colsum dZ1 --------------------------------------------------------------------------------
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        y.db[fb] += dbz[fb];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) y.dWt[fa][fb] = bk.mma16(kT[fa], dZ1p[fb], y.dWt[fa][fb]);
+    }
+}
+// dgamma / dbeta of (b, h): the per-lane partial sums over the four row groups
+template <class BK>
+TTT_WV_FN void store_ln_grads(BK& bk, const Lin16Params& p, int bh, const BwdCarry& y) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        const float dg = bk.xor_add(bk.xor_add(y.dgam[fb], 16), 32), dbt = bk.xor_add(bk.xor_add(y.dbet[fb], 16), 32);
+        if (g == 0) {
+            p.dln_w[(size_t)bh * 64 + 16 * fb + i] = dg;
+            p.dln_b[(size_t)bh * 64 + 16 * fb + i] = dbt;
+        }
+    }
+}
+// the eta row of a step: 16 bf16 in global memory -> fp32 in LDS
+template <class BK>
+TTT_WV_FN void park_eta(BK& bk, int l, unsigned short pe, int eta_off) {
+    if (l < 16) bk.template lds<float>(eta_off + l * 4) = (float)*reinterpret_cast<const __bf16*>(&pe);
 }
 
 template <class BK>
@@ -733,6 +1038,151 @@ TTT_WV_FN void backward(BK& bk, const Lin16Params& p, int bh) {
             }
         }
     }
+}
+
+// ===================================================================================================================
+// The backward in parts (Lin16BwdPartParams, ttt_wave_types.h).  The two halves of a checkpoint group's backward depend on
+// different things: the recompute on the group's checkpoint alone - every group of a sequence can be recomputed at once -, the
+// reverse walk on the gradient state the later groups leave.  recompute_groups is the first half, one wave per (b, h, group) of the
+// range, sweep_groups the second, one wave per (b, h) over the range; both run the steps of backward() above (as the functions
+// park_state / recompute_step / reverse_step), and the state a step reads is the same packed operands (a slot of the workspace
+// instead of the scratch / L_WHI), so the gradients are the bits of the one call however the K groups are cut into ranges.
+//
+// wave `bhk` = bh * nk + j recomputes group k0 + j of (b, h) = bh: slots 0 .. steps of the group, each with its bias row
+template <class BK>
+TTT_WV_FN void recompute_groups(BK& bk, const Lin16BwdPartParams& q, int bhk) {
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane();
+    const int NC = p.NC, G = p.G, K = p.K;
+    const int bh = bhk / q.nk, k = q.k0 + bhk % q.nk, head = bh % p.NH;
+    const int lo = k * G, hi = (lo + G < NC) ? lo + G : NC;
+    const size_t tile0 = (size_t)bh * NC;
+    char* slots = q.slots + (size_t)bhk * (G + 1) * LIN_PART_SLOT_BYTES;
+
+    BwdConsts c;
+    bwd_consts(bk, p, head, c);
+    f32x4 W1t[4][4];
+    float b1v[4];
+    load_matrix(bk, p.W1c + ((size_t)bh * K + k) * 64 * 64, W1t);
+    load_row(bk, p.b1c + ((size_t)bh * K + k) * 64, b1v);
+    Stage sk, sv;
+    unsigned short pe;
+    stage_request(bk, sk, p.XK + (tile0 + lo) * 1024);
+    stage_request(bk, sv, p.XV + (tile0 + lo) * 1024);
+    pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + lo) * 16 + (l0 & 15));
+    stage_park(bk, sk, L_K + (lo & 1) * TILE * 2);
+    stage_park(bk, sv, L_V + (lo & 1) * TILE * 2);
+    park_eta(bk, l0, pe, L_ETA + (lo & 1) * 64);
+    bk.lds_fence();
+    for (int it = lo; it <= hi; ++it) {          // iteration hi only parks the state that ends the group
+        const int buf = it & 1;
+        const int l = bk.opaque(l0), i = l & 15;
+        char* slot = slots + (size_t)(it - lo) * LIN_PART_SLOT_BYTES;
+        bf16x8 WF[2][4];
+        park_state(bk, W1t, slot, WF);
+        if ((l >> 4) == 0)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) reinterpret_cast<float*>(slot + SLOT_BYTES)[16 * fb + i] = b1v[fb];
+        if (it == hi) break;
+        const bool last = (it + 1 == hi);
+        if (!last) {        // K, V, eta of the next step
+            stage_request(bk, sk, p.XK + (tile0 + it + 1) * 1024);
+            stage_request(bk, sv, p.XV + (tile0 + it + 1) * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + it + 1) * 16 + (l & 15));
+        }
+        recompute_step(bk, l, c, L_K + buf * TILE * 2, L_V + buf * TILE * 2, L_ETA + buf * 64, WF, W1t, b1v);
+        if (!last) {
+            const int nb = buf ^ 1;
+            stage_park(bk, sk, L_K + nb * TILE * 2);
+            stage_park(bk, sv, L_V + nb * TILE * 2);
+            park_eta(bk, l, pe, L_ETA + nb * 64);
+        }
+        bk.lds_fence();
+    }
+}
+
+// the reverse walk of (b, h) = bh over the groups k0 + nk - 1 .. k0, from the slots recompute_groups left.  Carries dW1 / db1
+// (q.p.dW1_last / db1_last -> q.p.dW1 / db1) and the un-reduced dgamma / dbeta partial sums (q.ln_carry) from the range behind it to
+// the range in front of it; the range that holds group 0 also reduces the partial sums into dln_w / dln_b.  Consecutive steps
+// alternate tile buffers, so the tiles of the step in front are always parked in the middle of a step (the park-late case of
+// backward() - a next group whose first recomputed step shares the parity - does not arise: there is no recompute in between).
+template <class BK>
+TTT_WV_FN void sweep_groups(BK& bk, const Lin16BwdPartParams& q, int bh) {
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane();
+    const int NC = p.NC, G = p.G, K = p.K, head = bh % p.NH;
+    const int k0 = q.k0, nk = q.nk;
+    const int s_lo = k0 * G, s_hi = ((k0 + nk) * G < NC) ? (k0 + nk) * G : NC;      // the steps [s_lo, s_hi)
+    const size_t tile0 = (size_t)bh * NC;
+    const char* slots = q.slots + (size_t)bh * nk * (G + 1) * LIN_PART_SLOT_BYTES;
+    float* carry = q.ln_carry + (size_t)bh * LIN_PART_CARRY_FLOATS * 64 + l0;
+
+    BwdConsts c;
+    BwdCarry y;
+    load_matrix(bk, p.dW1_last + (size_t)bh * 64 * 64, y.dWt);
+    load_row(bk, p.db1_last + (size_t)bh * 64, y.db);
+    bwd_consts(bk, p, head, c);
+    if (k0 + nk == K) {      // the range that ends the sequence starts the sums
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) y.dgam[fb] = y.dbet[fb] = 0.f;
+    } else {
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) { y.dgam[fb] = carry[fb * 64]; y.dbet[fb] = carry[(4 + fb) * 64]; }
+    }
+    Stage sk, sv, sq, sd;
+    unsigned short pe = 0;
+    {   // tiles of the first step of the walk: the combined kernel gets these from its recompute loop
+        const int s0 = s_hi - 1, o = (s0 & 1) * TILE * 2;
+        stage_request(bk, sk, p.XK + (tile0 + s0) * 1024);
+        stage_request(bk, sv, p.XV + (tile0 + s0) * 1024);
+        stage_request(bk, sq, p.XQ + (tile0 + s0) * 1024);
+        stage_request(bk, sd, p.dOut + (tile0 + s0) * 1024);
+        pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + s0) * 16 + (l0 & 15));
+        stage_park(bk, sk, L_K + o); stage_park(bk, sv, L_V + o); stage_park(bk, sq, L_Q + o); stage_park(bk, sd, L_D + o);
+        park_eta(bk, l0, pe, L_ETA + (s0 & 1) * 64);
+        bk.lds_fence();
+    }
+    int k = k0 + nk - 1, lo = k * G;          // the group of step `it`
+    for (int it = s_hi - 1; it >= s_lo; --it) {
+        if (it < lo) { --k; lo -= G; }
+        const int buf = it & 1, nb = buf ^ 1;
+        const int l = bk.opaque(l0), i = l & 15;
+        const bool more = it > s_lo;
+        if (more) {
+            stage_request(bk, sk, p.XK + (tile0 + it - 1) * 1024);
+            stage_request(bk, sv, p.XV + (tile0 + it - 1) * 1024);
+            stage_request(bk, sq, p.XQ + (tile0 + it - 1) * 1024);
+            stage_request(bk, sd, p.dOut + (tile0 + it - 1) * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + it - 1) * 16 + (l & 15));
+        }
+        const char* slot = slots + ((size_t)(k - k0) * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;       // state entering the step
+        const char* slot_n = slot + LIN_PART_SLOT_BYTES;                                                 // ... and after it
+        float b1v[4], b1n[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            b1v[fb] = reinterpret_cast<const float*>(slot + SLOT_BYTES)[16 * fb + i];
+            b1n[fb] = reinterpret_cast<const float*>(slot_n + SLOT_BYTES)[16 * fb + i];
+        }
+        reverse_step(bk, l, p, c, y, tile0 + it, L_K + buf * TILE * 2, L_V + buf * TILE * 2, L_Q + buf * TILE * 2, L_D + buf * TILE * 2,
+                     L_ETA + buf * 64, slot, slot_n, b1v, b1n, [&] {
+                         if (more) {
+                             stage_park(bk, sk, L_K + nb * TILE * 2); stage_park(bk, sv, L_V + nb * TILE * 2);
+                             stage_park(bk, sq, L_Q + nb * TILE * 2); stage_park(bk, sd, L_D + nb * TILE * 2);
+                             park_eta(bk, l, pe, L_ETA + nb * 64);
+                         }
+                     });
+        bk.lds_fence();
+    }
+    // ---- hand-over.  q.p.dW1 / db1 MAY ALIAS dW1_last / db1_last (the caller carries the gradient state in place): this wave is the
+    // only reader of its (b, h)'s dW1_last / db1_last and read all of it before the first step.  ln_carry is read (above) and written
+    // by the same lane only.
+    store_matrix(bk, p.dW1 + (size_t)bh * 64 * 64, y.dWt);
+    if ((l0 >> 4) == 0)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) p.db1[(size_t)bh * 64 + 16 * fb + (l0 & 15)] = y.db[fb];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) { carry[fb * 64] = y.dgam[fb]; carry[(4 + fb) * 64] = y.dbet[fb]; }
+    if (k0 == 0) store_ln_grads(bk, p, bh, y);
 }
 
 }  // namespace lin16

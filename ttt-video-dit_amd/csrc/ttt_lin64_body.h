@@ -302,10 +302,251 @@ TTT_WV_FN void forward(BK& bk, const Lin16Params& p, int bh) {
     forward_part(bk, c, bh);
 }
 
+// ---- the pieces of the backward in parts (recompute_groups / sweep_groups, behind backward() below): the steps of backward() as
+// functions ; backward() keeps them inline and lin16::fma4 fixes the fused products its compiled code takes (see ttt_lin16_body.h) ------
+// what a sweep carries from step to step
+struct BwdCarry {
+    f32x4 dWt[4];         // [fa]  dW1[16fa + 4g + r][16w + i]
+    float db[4];          // db1[16fb + i], the same in every wave
+    float dgam[4], dbet[4];     // per-lane partial sums over this lane's token rows
+};
+// this wave's column slice of a [64][64] fp32 matrix in global memory <-> tiles T[fa]
+template <class BK>
+TTT_WV_FN void load_slice(BK& bk, int w, const float* M, f32x4 (&T)[4]) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) T[fa][r] = M[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * w + i];
+}
+template <class BK>
+TTT_WV_FN void store_slice(BK& bk, int w, float* M, const f32x4 (&T)[4]) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fa = 0; fa < 4; ++fa)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) M[(size_t)(16 * fa + 4 * g + r) * 64 + 16 * w + i] = T[fa][r];
+}
+// parks the state (every wave its slice W1t) as packed operands in both orientations at `slot`: publishes the L_WI / L_TR images,
+// barrier R1 (L_WI, L_TR written | read), then wave w stores the four fragments of its slice
+template <class BK>
+TTT_WV_FN void park_state(BK& bk, int w, const f32x4 (&W1t)[4], char* slot) {
+    bf16x8 mine[2];
+    publish_slice(bk, w, W1t, mine);
+    publish_transposed(bk, w, W1t);
+    bk.barrier();                                           // R1: L_WI, L_TR written | read
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        lin16::st_pack(bk, slot, ks * 4 + w, mine[ks]);
+        lin16::st_pack(bk, slot, 8 + ks * 4 + w, transposed_frag(bk, ks, 16 * w));
+    }
+}
+// one recomputed step from the L_WI image park_state published: this wave's tokens through the inner step, barrier R2, the update
+// of its slice.  Kb / Vb: the K / V tiles of the mini-batch (all four waves' rows).
+template <class BK>
+TTT_WV_FN void recompute_step(BK& bk, int w, const Consts& c, float eps, int Kb, int Vb, int eta_off, f32x4 (&W1t)[4], float (&b1v)[4]) {
+    {
+        bf16x8 Wp[8];
+        load_image(bk, Wp);
+        inner_publish(bk, w, Kb + w * TILE_B, Vb + w * TILE_B, eta_off, Wp, b1v, c, eps);
+    }
+    bk.barrier();                                           // R2: L_X, L_PS written | read (until R1 of the next step)
+    update_slice(bk, w, Kb, L_X, L_PS, W1t, b1v);
+}
+// one step of the reverse walk (step numbers (n): oracle/ttt_oracle.py:_lin_step_bwd in the order lin16 lists them).  Kb .. Db: the
+// tiles of the mini-batch, eta_off: this wave's eta ; slot / b1v: the state entering the step, slot_n / b1n: the state after it ; y:
+// the carried gradients ; `tile`: the step's tile of the whole sequence.  `mid()` runs between barriers A and B: where the caller parks
+// the tiles it requested for the next step into the other buffer, which was last read (K in (10), Q in (3)) by the step before this
+// one.  Ends with the carried update (10); the caller fences LDS behind it.
+template <class BK, class Mid>
+TTT_WV_FN void reverse_step(BK& bk, int l, int w, const Lin16Params& p, const Consts& c, BwdCarry& y, size_t tile, int Kb, int Vb, int Qb,
+                            int Db, int eta_off, const char* slot, const char* slot_n, const float (&b1v)[4], const float (&b1n)[4],
+                            Mid&& mid) {
+    const int g = l >> 4, i = l & 15;
+    const int IMG = L_IMG + w * 2 * IMG_BYTES, own = w * TILE_B;
+    const int Kt = Kb + own, Vt = Vb + own, Qt = Qb + own, Dt = Db + own;
+    const f32x4 eta4 = bk.template lds<f32x4>(eta_off + 4 * g * 4);
+    // ---- (2) outer LayerNorm backward for this wave's tokens: Z1b = Q W1n + b1n ; dZ1b -> L_X, its column sums -> L_PS ------
+    f32x4 dq[4];                     // starts as dOut (accumulator layout), becomes dQ
+    {
+        bf16x4 dZbp[4];
+        float cs[4];
+        const bf16x8 qA0 = lin16::rho_read(bk, Qt, 0), qA1 = lin16::rho_read(bk, Qt, 32);
+        f32x4 yy[4], dxl[4], t2[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            f32x4 a = zero4();
+            a = bk.mma32(qA0, lin16::ld_pack(bk, slot_n, fb), a);
+            a = bk.mma32(qA1, lin16::ld_pack(bk, slot_n, 4 + fb), a);
+            yy[fb] = a + b1n[fb];
+            dq[fb] = bk.mma16(c.IDP, lin16::tr4(bk, Dt, TS, 0, 16 * fb), zero4());                // exact dOut
+        }
+        const f32x4 rstdl = lin16::normalize_rows(bk, yy, p.eps);                                 // yy <- x_hat of the output LN
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dx = dq[fb] * yy[fb];
+            y.dgam[fb] += dx[0] + dx[1] + dx[2] + dx[3];
+            y.dbet[fb] += dq[fb][0] + dq[fb][1] + dq[fb][2] + dq[fb][3];
+            dxl[fb] = dq[fb] * c.gam[fb];
+            t2[fb] = dxl[fb] * yy[fb];
+        }
+        const f32x4 u1 = lin16::rowsum64(bk, dxl), u2 = lin16::rowsum64(bk, t2);
+        const f32x4 sc = rstdl * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dzb = (64.0f * dxl[fb] - u1 - yy[fb] * u2) * sc;
+            dZbp[fb] = pack4(dzb);
+            cs[fb] = lin16::colsum16(bk, dzb);                                                    // fp32 sums, as at mini-batch 16
+        }
+        publish_rows(bk, w, L_X, L_PS, dZbp, cs);
+        // ---- (4) dQ = dOut + dZ1b W1n^T --------------------------------------------------------------------------------------
+        bf16x8 aZ[2];
+        lin16::image_of(bk, IMG, dZbp, aZ);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dq[fa] = bk.mma32(aZ[0], lin16::ld_pack(bk, slot_n, 8 + fa), dq[fa]);
+            dq[fa] = bk.mma32(aZ[1], lin16::ld_pack(bk, slot_n, 12 + fa), dq[fa]);
+        }
+        lin16::store_rows(bk, IMG + IMG_BYTES, dq, p.dXQ + tile * 4096 + w * 1024);
+    }
+    bk.lds_fence();
+    // ---- (1) inner forward of the step for this wave's tokens: Z1 = K W + b, LN / L2 gradient ------------------------------
+    const bf16x8 kA0 = lin16::rho_read(bk, Kt, 0), kA1 = lin16::rho_read(bk, Kt, 32);
+    bf16x4 kT[4];
+    InnerGrad ig;
+    {
+        f32x4 z[4], tg[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            kT[fb] = lin16::tr4(bk, Kt, TS, 0, 16 * fb);
+            f32x4 a = zero4();
+            a = bk.mma32(kA0, lin16::ld_pack(bk, slot, fb), a);
+            a = bk.mma32(kA1, lin16::ld_pack(bk, slot, 4 + fb), a);
+            z[fb] = a + b1v[fb];
+            tg[fb] = bk.mma16(c.IDN, kT[fb], bk.mma16(c.IDP, lin16::tr4(bk, Vt, TS, 0, 16 * fb), zero4()));   // exact V - K
+        }
+        lin16::inner_grad(bk, z, tg, c.gam, c.bet, p.eps, ig);
+    }
+    bk.barrier();                                               // A: L_X, L_PS written | read ; every wave has left the step before
+    // ---- (3) dW1n += Q^T dZ1b ; db1n += colsum dZ1b ; the images of dW1n -----------------------------------------------------
+    update_slice(bk, w, Qb, L_X, L_PS, y.dWt, y.db);
+    {
+        bf16x8 mine[2];
+        publish_slice(bk, w, y.dWt, mine);
+        publish_transposed(bk, w, y.dWt);
+    }
+    mid();
+    bk.barrier();                                               // B: L_WI, L_TR written | read (until A of the next step)
+    // ---- (6) dgZ1 = -eta (K dW1n + db1n) ; (8) backward of the fused LN / L2 gradient -> dZ1, dt, dgamma, dbeta -----------------
+    bf16x4 dZ1p[4];
+    f32x4 dk[4];                     // starts as -dt (dt = gradient w.r.t. the target V - K = dV)
+    {
+        f32x4 dgz[4], mGr[4], t2[4];
+        {
+            bf16x8 DWp[8];
+            load_image(bk, DWp);
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) {
+                f32x4 a = zero4();
+                a = bk.mma32(kA0, DWp[fb], a);
+                a = bk.mma32(kA1, DWp[4 + fb], a);
+                dgz[fb] = (a + y.db[fb]) * (-eta4);
+                mGr[fb] = dgz[fb] * (-ig.rstd);
+                t2[fb] = mGr[fb] * ig.xh[fb];
+            }
+        }
+        const f32x4 s1 = lin16::rowsum64(bk, mGr) * (1.0f / 64.0f), s2 = lin16::rowsum64(bk, t2) * (1.0f / 64.0f);
+        const f32x4 c2 = ig.s2g * (1.0f / 64.0f);
+        f32x4 dxh[4], dstd[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dgxh = lin16::fma4(dgz[fb], ig.rstd, s1) + ig.xh[fb] * s2;
+            const f32x4 dy = dgxh * c.gam[fb];
+            const f32x4 dg = lin16::fma4(ig.go[fb], dgxh, dy * ig.xh[fb]);
+            y.dgam[fb] += dg[0] + dg[1] + dg[2] + dg[3];
+            y.dbet[fb] += dy[0] + dy[1] + dy[2] + dy[3];
+            dk[fb] = dy;                                                                       // = -dt
+            dxh[fb] = lin16::fma4(ig.go[fb] * c.gam[fb], s2, dy * c.gam[fb]) + mGr[fb] * c2;
+            dstd[fb] = lin16::fma4(dgz[fb], ig.gz[fb], dxh[fb] * ig.xh[fb]) * (-ig.rstd);
+        }
+        const f32x4 v1 = lin16::rowsum64(bk, dxh) * (1.0f / 64.0f), v2 = lin16::rowsum64(bk, dstd) * (1.0f / 64.0f);
+        float cs[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dz1 = lin16::fma4(dxh[fb] - v1, ig.rstd, ig.xh[fb] * v2);
+            dZ1p[fb] = pack4(dz1);
+            cs[fb] = lin16::colsum16(bk, dz1);
+        }
+        publish_rows(bk, w, L_X2, L_PS2, dZ1p, cs);                                               // for (10)
+        f32x4 dv[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) dv[fb] = -dk[fb];
+        lin16::store_rows(bk, IMG + IMG_BYTES, dv, p.dXV + tile * 4096 + w * 1024);              // dV = dt
+    }
+    bk.lds_fence();
+    // ---- (5, 7, 9) A1 = gZ1 dW1n^T ; d eta ; dK = -eta A1 - dt + dZ1 W^T --------------------------------------------------------------
+    {
+        bf16x4 gzq[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) gzq[fb] = pack4(ig.gz[fb]);
+        bf16x8 aG[2];
+        lin16::image_of(bk, IMG, gzq, aG);
+        f32x4 acc[4];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            f32x4 a1 = zero4();
+            a1 = bk.mma32(aG[0], transposed_frag(bk, 0, 16 * fa), a1);
+            a1 = bk.mma32(aG[1], transposed_frag(bk, 1, 16 * fa), a1);
+            dk[fa] -= a1 * eta4;
+            const f32x4 kc = bk.mma16(c.IDP, kT[fa], zero4());                                // exact K, accumulator layout
+            acc[fa] = lin16::fma4(ig.gz[fa], lin16::splat4(y.db[fa]), kc * a1);
+        }
+        const f32x4 de = lin16::rowsum64(bk, acc);
+        if (i == 0) *reinterpret_cast<bf16x4*>(p.deta + tile * 64 + 16 * w + 4 * g) = pack4(-de);
+    }
+    bk.lds_fence();
+    {
+        bf16x8 aD[2];
+        lin16::image_of(bk, IMG, dZ1p, aD);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dk[fa] = bk.mma32(aD[0], lin16::ld_pack(bk, slot, 8 + fa), dk[fa]);
+            dk[fa] = bk.mma32(aD[1], lin16::ld_pack(bk, slot, 12 + fa), dk[fa]);
+        }
+        lin16::store_rows(bk, IMG + IMG_BYTES, dk, p.dXK + tile * 4096 + w * 1024);
+    }
+    bk.barrier();                                               // C: L_X2, L_PS2 written | read (until B of the next step)
+    // ---- (10) dW1 = dW1n + K^T dZ1 ; db1 = db1n + colsum dZ1 --------------------------------------------------------------------------
+    update_slice(bk, w, Kb, L_X2, L_PS2, y.dWt, y.db);
+}
+// dgamma / dbeta of (b, h): the per-lane partial sums over the lane groups, then over the waves through L_X (last read in (3) of
+// the last step, two barriers back)
+template <class BK>
+TTT_WV_FN void store_ln_grads(BK& bk, int w, const Lin16Params& p, int bh, const BwdCarry& y) {
+    const int g = bk.lane() >> 4, i = bk.lane() & 15;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        const float dg = bk.xor_add(bk.xor_add(y.dgam[fb], 16), 32), dbt = bk.xor_add(bk.xor_add(y.dbet[fb], 16), 32);
+        if (g == 0) {
+            bk.template lds_store<float>(L_X + (w * 64 + 16 * fb + i) * 4, dg);
+            bk.template lds_store<float>(L_X + 1024 + (w * 64 + 16 * fb + i) * 4, dbt);
+        }
+    }
+    bk.barrier();
+    if (w == 0 && g == 0)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const int o = L_X + (16 * fb + i) * 4;
+            p.dln_w[(size_t)bh * 64 + 16 * fb + i] = (bk.template lds_load<float>(o) + bk.template lds_load<float>(o + 256)) +
+                                                     (bk.template lds_load<float>(o + 512) + bk.template lds_load<float>(o + 768));
+            p.dln_b[(size_t)bh * 64 + 16 * fb + i] = (bk.template lds_load<float>(o + 1024) + bk.template lds_load<float>(o + 1280)) +
+                                                     (bk.template lds_load<float>(o + 1536) + bk.template lds_load<float>(o + 1792));
+        }
+}
+
 // ===================================================================================================================
 // backward of the scan of (b, h) = bh: checkpoint groups from the last to the first, each re-run forward (parking the state that
-// enters every step) and then walked in reverse, as in lin16::backward.  Step numbers (n) refer to oracle/ttt_oracle.py:_lin_step_bwd
-// in the order lin16 lists them.
+// enters every step) and then walked in reverse, as in lin16::backward.
 template <class BK>
 TTT_WV_FN void backward(BK& bk, const Lin16Params& p, int bh) {
     const int l0 = bk.lane(), w = bk.wave();
@@ -629,6 +870,153 @@ TTT_WV_FN void backward(BK& bk, const Lin16Params& p, int bh) {
                                                          (bk.template lds_load<float>(o + 1536) + bk.template lds_load<float>(o + 1792));
             }
     }
+}
+
+// ===================================================================================================================
+// The backward in parts (Lin16BwdPartParams, ttt_wave_types.h ; see lin16::recompute_groups / sweep_groups): the same two entries
+// with a workgroup of four waves in place of the wave, running the steps of backward() above as functions.  The state that ends a group is a
+// slot of the workspace like every other (no L_WHI), written and read in different kernels; within recompute_groups no wave reads a
+// slot, within sweep_groups no wave writes one.
+//
+// workgroup `bhk` = bh * nk + j recomputes group k0 + j of (b, h) = bh
+template <class BK>
+TTT_WV_FN void recompute_groups(BK& bk, const Lin16BwdPartParams& q, int bhk) {
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane(), w = bk.wave();
+    const int NC = p.NC, G = p.G, K = p.K;
+    const int bh = bhk / q.nk, k = q.k0 + bhk % q.nk, head = bh % p.NH;
+    const int lo = k * G, hi = (lo + G < NC) ? lo + G : NC;
+    const size_t tile0 = (size_t)bh * NC;
+    const int ETA = L_ETA + w * 128, own = w * TILE_B;
+    char* slots = q.slots + (size_t)bhk * (G + 1) * LIN_PART_SLOT_BYTES;
+
+    Consts c;
+    make_consts(bk, p, head, c);
+    f32x4 W1t[4];
+    float b1v[4];
+    load_slice(bk, w, p.W1c + ((size_t)bh * K + k) * 64 * 64, W1t);
+    lin16::load_row(bk, p.b1c + ((size_t)bh * K + k) * 64, b1v);
+    int cur = 0;
+    Stage sk, sv;
+    unsigned short pe;
+    lin16::stage_request(bk, sk, p.XK + (tile0 + lo) * 4096 + w * 1024);
+    lin16::stage_request(bk, sv, p.XV + (tile0 + lo) * 4096 + w * 1024);
+    pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + lo) * 64 + 16 * w + (l0 & 15));
+    park(bk, sk, L_K + own); park(bk, sv, L_V + own);       // (other waves read these K rows behind R1 and R2 of the first step)
+    park_eta(bk, pe, ETA);
+    bk.lds_fence();
+    for (int it = lo; it <= hi; ++it) {          // iteration hi only parks the state that ends the group
+        const int l = bk.opaque(l0), i = l & 15;
+        char* slot = slots + (size_t)(it - lo) * LIN_PART_SLOT_BYTES;
+        park_state(bk, w, W1t, slot);
+        if (w == 0 && (l >> 4) == 0)
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) reinterpret_cast<float*>(slot + SLOT_BYTES)[16 * fb + i] = b1v[fb];
+        if (it == hi) break;
+        const bool last = (it + 1 == hi);
+        if (!last) {        // K, V, eta of the next step
+            const size_t t = tile0 + it + 1;
+            lin16::stage_request(bk, sk, p.XK + t * 4096 + w * 1024);
+            lin16::stage_request(bk, sv, p.XV + t * 4096 + w * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + t * 64 + 16 * w + (l & 15));
+        }
+        recompute_step(bk, w, c, p.eps, L_K + cur * T64_B, L_V + cur * T64_B, ETA + cur * 64, W1t, b1v);
+        if (!last) {        // (the other buffer's K tiles were last read by other waves before R1 of this step)
+            const int nb = cur ^ 1;
+            park(bk, sk, L_K + nb * T64_B + own); park(bk, sv, L_V + nb * T64_B + own);
+            park_eta(bk, pe, ETA + nb * 64);
+            cur = nb;
+        }
+        bk.lds_fence();
+    }
+}
+
+// the reverse walk of (b, h) = bh over the groups k0 + nk - 1 .. k0 from the slots recompute_groups left ; carries as in
+// lin16::sweep_groups (the partial sums of dgamma / dbeta per lane of each of the four waves)
+template <class BK>
+TTT_WV_FN void sweep_groups(BK& bk, const Lin16BwdPartParams& q, int bh) {
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane(), w = bk.wave();
+    const int NC = p.NC, G = p.G, K = p.K, head = bh % p.NH;
+    const int k0 = q.k0, nk = q.nk;
+    const int s_lo = k0 * G, s_hi = ((k0 + nk) * G < NC) ? (k0 + nk) * G : NC;      // the steps [s_lo, s_hi)
+    const size_t tile0 = (size_t)bh * NC;
+    const int ETA = L_ETA + w * 128, own = w * TILE_B;
+    const char* slots = q.slots + (size_t)bh * nk * (G + 1) * LIN_PART_SLOT_BYTES;
+    float* carry = q.ln_carry + (size_t)bh * LIN_PART_CARRY_FLOATS * 64 * WAVES + w * 64 + l0;
+
+    Consts c;
+    make_consts(bk, p, head, c);
+    BwdCarry y;
+    load_slice(bk, w, p.dW1_last + (size_t)bh * 64 * 64, y.dWt);
+    lin16::load_row(bk, p.db1_last + (size_t)bh * 64, y.db);
+    if (k0 + nk == K) {      // the range that ends the sequence starts the sums
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) y.dgam[fb] = y.dbet[fb] = 0.f;
+    } else {
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) { y.dgam[fb] = carry[fb * 64 * WAVES]; y.dbet[fb] = carry[(4 + fb) * 64 * WAVES]; }
+    }
+    int cur = 0;
+    Stage sk, sv, sq, sd;
+    unsigned short pe = 0;
+    {   // tiles of the first step of the walk: the combined kernel gets these from its recompute loop.  Every wave its own rows; the
+        // rows of other waves are read behind barrier A of the first step at the earliest (Q in (3), K in (10)).
+        const size_t t = tile0 + s_hi - 1;
+        lin16::stage_request(bk, sk, p.XK + t * 4096 + w * 1024);
+        lin16::stage_request(bk, sv, p.XV + t * 4096 + w * 1024);
+        lin16::stage_request(bk, sq, p.XQ + t * 4096 + w * 1024);
+        lin16::stage_request(bk, sd, p.dOut + t * 4096 + w * 1024);
+        pe = *reinterpret_cast<const unsigned short*>(p.eta + t * 64 + 16 * w + (l0 & 15));
+        park(bk, sk, L_K + own); park(bk, sv, L_V + own); park(bk, sq, L_Q + own); park(bk, sd, L_D + own);
+        park_eta(bk, pe, ETA);
+        bk.lds_fence();
+    }
+    int k = k0 + nk - 1, lo = k * G;          // the group of step `it`
+    for (int it = s_hi - 1; it >= s_lo; --it) {
+        if (it < lo) { --k; lo -= G; }
+        const int l = bk.opaque(l0), i = l & 15;
+        const bool more = it > s_lo;
+        if (more) {
+            const size_t t = tile0 + it - 1;
+            lin16::stage_request(bk, sk, p.XK + t * 4096 + w * 1024);
+            lin16::stage_request(bk, sv, p.XV + t * 4096 + w * 1024);
+            lin16::stage_request(bk, sq, p.XQ + t * 4096 + w * 1024);
+            lin16::stage_request(bk, sd, p.dOut + t * 4096 + w * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + t * 64 + 16 * w + (l & 15));
+        }
+        const char* slot = slots + ((size_t)(k - k0) * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;       // state entering the step
+        const char* slot_n = slot + LIN_PART_SLOT_BYTES;                                                 // ... and after it
+        float b1v[4], b1n[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            b1v[fb] = reinterpret_cast<const float*>(slot + SLOT_BYTES)[16 * fb + i];
+            b1n[fb] = reinterpret_cast<const float*>(slot_n + SLOT_BYTES)[16 * fb + i];
+        }
+        reverse_step(bk, l, w, p, c, y, tile0 + it, L_K + cur * T64_B, L_V + cur * T64_B, L_Q + cur * T64_B, L_D + cur * T64_B,
+                     ETA + cur * 64, slot, slot_n, b1v, b1n, [&] {
+                         if (more) {
+                             const int nb = cur ^ 1;
+                             park(bk, sk, L_K + nb * T64_B + own); park(bk, sv, L_V + nb * T64_B + own);
+                             park(bk, sq, L_Q + nb * T64_B + own); park(bk, sd, L_D + nb * T64_B + own);
+                             park_eta(bk, pe, ETA + nb * 64);
+                         }
+                     });
+        if (more) cur ^= 1;
+        bk.lds_fence();
+    }
+    // ---- hand-over.  q.p.dW1 / db1 MAY ALIAS dW1_last / db1_last (the caller carries the gradient state in place).  Global memory, so
+    // the emulator's race detector does not see this one; it rests on the barriers: every wave reads db1_last and its own slice of
+    // dW1_last in front of the step loop, and these stores come behind barriers A, B and C of the last step (a range has at least one
+    // step) - no wave can still be reading, and a wave overwrites only the slice that it alone read.  ln_carry is read (above) and
+    // written by the same lane only.
+    store_slice(bk, w, p.dW1 + (size_t)bh * 64 * 64, y.dWt);
+    if (w == 0 && (l0 >> 4) == 0)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) p.db1[(size_t)bh * 64 + 16 * fb + (l0 & 15)] = y.db[fb];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) { carry[fb * 64 * WAVES] = y.dgam[fb]; carry[(4 + fb) * 64 * WAVES] = y.dbet[fb]; }
+    if (k0 == 0) store_ln_grads(bk, w, p, bh, y);
 }
 
 }  // namespace lin64

@@ -74,7 +74,7 @@ void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int s
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipStream_t s) {
     linear_forward_chunk(d, a, 0, d->NC, nullptr, nullptr, s);
 }
-void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hipStream_t s) {
+static wv::Lin16Params linear_bwd_params(const ttt_dims* d, const ttt_linear_bwd_args* a) {
     wv::Lin16Params p = {};
     p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
     p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
@@ -86,8 +86,28 @@ void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hip
     p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init;
     p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
     p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    return p;
+}
+void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hipStream_t s) {
+    const wv::Lin16Params p = linear_bwd_params(d, a);
     if (d->CS == 16) launch_linear_backward_cs16(p, d->B * d->NH, s);
     else launch_linear_backward_cs64(p, d->B * d->NH, s);
+}
+// The backward in parts (ttt_wave_types.h: Lin16BwdPartParams).  G + 1 slots per group: the state entering each step and the state
+// that ends the group ; the carry: 8 partial sums per lane of the scan's wave (CS = 16) or four waves (CS = 64).
+size_t linear_backward_parts_slots(const ttt_dims* d, int nk) {
+    return (size_t)d->B * d->NH * (size_t)nk * (size_t)(d->G + 1) * wv::LIN_PART_SLOT_BYTES;
+}
+size_t linear_backward_parts_carry(const ttt_dims* d) {
+    return (size_t)d->B * d->NH * wv::LIN_PART_CARRY_FLOATS * (d->CS == 16 ? 64 : 256) * sizeof(float);
+}
+void linear_recompute_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, void* slots, hipStream_t s) {
+    const wv::Lin16BwdPartParams q = {linear_bwd_params(d, a), k0, nk, (char*)slots, nullptr};
+    launch_linear_recompute_groups(q, d->CS, d->B * d->NH, s);
+}
+void linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, float* ln_carry, hipStream_t s) {
+    const wv::Lin16BwdPartParams q = {linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry};
+    launch_linear_sweep_groups(q, d->CS, d->B * d->NH, s);
 }
 
 }  // namespace mfma

@@ -174,6 +174,31 @@ __global__ __launch_bounds__(64 * lin64::WAVES) void linear_bwd_cs64_kernel(wv::
     lin64::backward(bk, p, blockIdx.x);
 }
 
+
+// The TTT-Linear backward in parts (lin16:: / lin64::recompute_groups, sweep_groups): the recompute of a range of checkpoint groups,
+// one wave (mini-batches of 16) or one four-wave workgroup (of 64) per (b, h, group), and the reverse walk over the range from the
+// slots it left, one per (b, h).  Neither keeps the state that ends a group in LDS: their LDS ends where L_WHI begins.
+__global__ __launch_bounds__(64) void linear_recompute16_groups_kernel(wv::Lin16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin16::recompute_groups(bk, q, blockIdx.x);
+}
+__global__ __launch_bounds__(64) void linear_sweep16_groups_kernel(wv::Lin16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin16::sweep_groups(bk, q, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * lin64::WAVES) void linear_recompute_cs64_groups_kernel(wv::Lin16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin64::recompute_groups(bk, q, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * lin64::WAVES) void linear_sweep_cs64_groups_kernel(wv::Lin16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin64::sweep_groups(bk, q, blockIdx.x);
+}
+
 }  // namespace v16
 
 static void lin_attr_once() {
@@ -207,6 +232,26 @@ void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStre
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
     lin64_attr_once();
     hipLaunchKernelGGL(v16::linear_bwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS_BWD, s, p);
+}
+
+static void lin_parts_attr_once() {
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::linear_recompute16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::L_WHI);
+        (void)hipFuncSetAttribute((const void*)v16::linear_sweep16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::L_WHI);
+        (void)hipFuncSetAttribute((const void*)v16::linear_recompute_cs64_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::L_WHI);
+        (void)hipFuncSetAttribute((const void*)v16::linear_sweep_cs64_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::L_WHI);
+    });
+}
+void launch_linear_recompute_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s) {
+    lin_parts_attr_once();
+    if (cs == 16) hipLaunchKernelGGL(v16::linear_recompute16_groups_kernel, dim3(n_bh * q.nk), dim3(64), lin16::L_WHI, s, q);
+    else hipLaunchKernelGGL(v16::linear_recompute_cs64_groups_kernel, dim3(n_bh * q.nk), dim3(64 * lin64::WAVES), lin64::L_WHI, s, q);
+}
+void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s) {
+    lin_parts_attr_once();
+    if (cs == 16) hipLaunchKernelGGL(v16::linear_sweep16_groups_kernel, dim3(n_bh), dim3(64), lin16::L_WHI, s, q);
+    else hipLaunchKernelGGL(v16::linear_sweep_cs64_groups_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::L_WHI, s, q);
 }
 
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*, hipStream_t s) {

@@ -50,6 +50,9 @@ void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStre
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h); whole sequence or a part
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);
+// TTT-Linear backward in parts at mini-batches `cs` = 16 / 64: recompute grid n_bh * q.nk, sweep grid n_bh
+void launch_linear_recompute_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s);
+void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s);
 void set_debug_dump(float* buf);
 unsigned long long* get_debug_timing();
 void set_debug_overlap_tail(int v);   // backward schedule: 0 one stream, 1 tail of chunk c beside the sweep of chunk c-1, 2 (default) the next recompute too

@@ -44,6 +44,22 @@ struct Lin16ChunkParams {
     float *W1f, *b1f;
 };
 
+// the TTT-Linear backward in parts (ttt_lin16_body.h / ttt_lin64_body.h: recompute_groups, sweep_groups): the checkpoint groups
+// [k0, k0 + nk) of the K = p.K groups of the sequence that `p` describes (whole-sequence pointers; p.scratch_w / p.scratch_b unused).
+// `slots`: [B*NH][nk][G + 1] slots of LIN_PART_SLOT_BYTES - slot j of a group is the state ENTERING its step j as packed operands in
+// both orientations (the 16 KiB of lin16::SLOT_BYTES) followed by the bias row (64 fp32); slot `steps of the group` is the state that
+// ends it (a ragged last group uses fewer than G + 1).  recompute_groups writes them from the checkpoints, sweep_groups reads them.
+// `ln_carry`: [B*NH][8][lanes of the scan] fp32, the un-reduced per-lane partial sums of dgamma (rows 0..3) and dbeta (4..7) - 64 lanes
+// at mini-batches of 16, 256 at mini-batches of 64 (LIN_PART_CARRY_FLOATS per lane) - handed from one sweep_groups call to the next.
+constexpr size_t LIN_PART_SLOT_BYTES = 16 * 1024 + 64 * sizeof(float);
+constexpr int LIN_PART_CARRY_FLOATS = 8;
+struct Lin16BwdPartParams {
+    Lin16Params p;
+    int k0, nk;
+    char* slots;
+    float* ln_carry;
+};
+
 // arguments of the TTT-MLP forward scan at mini-batches of 16 tokens (F = 64, hidden 256)
 struct Mlp16Params {
     const __bf16 *XQ, *XK, *XV, *eta;

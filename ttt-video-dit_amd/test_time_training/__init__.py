@@ -153,6 +153,14 @@ EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 _PROTOTYPES_PARTS = {
     "ttt_hip_linear_forward_chunk": _sig("2p 2i 3p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_bwd_parts.h, the third header: the TTT-Linear backward over ranges of checkpoint
+# groups (tests/test_abi_bwd_parts_cpu.py compares the two)
+_PROTOTYPES_BWD_PARTS = {
+    "ttt_hip_linear_backward_parts_slots": _sig("p i", ctypes.c_size_t),
+    "ttt_hip_linear_backward_parts_carry": _sig("p", ctypes.c_size_t),
+    "ttt_hip_linear_recompute_groups": _sig("2p 2i p z p"),
+    "ttt_hip_linear_sweep_groups": _sig("2p 2i p z p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -174,7 +182,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(_LIB_PATH)
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -483,6 +491,93 @@ def ttt_linear_backward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_no
                grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
                grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
     _launch("ttt_hip_linear_backward", *_scan_args(_LinBwd, _LIN_BWD_SPEC, tensors, checkpoint_group_size, impl=impl))
+
+
+# The TTT-Linear backward over ranges of checkpoint groups (include/ttt_hip_bwd_parts.h).  The recompute reads XK, XV, last_eta, the
+# LayerNorm parameters and the checkpoints; the sweep reads and writes everything else of ``ttt_linear_backward``'s list.  What a call
+# does not touch may be None; what is given is checked against the contract of ``ttt_linear_backward``, field by field.
+_LIN_RECOMPUTE_FIELDS = frozenset(("XK", "XV", "last_eta", "ttt_norm_weight", "ttt_norm_bias", "W1_checkpoints", "b1_checkpoints"))
+_LIN_SWEEP_UNUSED = frozenset(("W1_checkpoints", "b1_checkpoints", "W1_init_group", "b1_init_group"))
+linear_bwd_parts_calls = {"recompute": 0, "sweep": 0}      # launches of this process (tests, tools)
+
+
+def _lin_bwd_part_args(impl, tensors, checkpoint_group_size, optional):
+    XQ = tensors[0] if tensors[0] is not None else tensors[1]          # (the recompute does not need XQ: XK has its shape)
+    _check5(XQ)
+    B, NH, NC, CS, F = XQ.shape
+    G = int(checkpoint_group_size)
+    sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
+    args = _fill_args(_LinBwd, _LIN_BWD_SPEC, tensors, sizes, XQ.dtype, optional)
+    return _dims(B, NH, NC, CS, F, G, XQ.dtype, impl), args, XQ.device
+
+
+def _device_bytes(t, name):
+    """a raw workspace: any dtype; the library checks its size against the range of the call"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor on a HIP device")
+
+
+def linear_backward_parts_slots(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of the slot workspace of ``ttt_linear_recompute_groups`` / ``ttt_linear_sweep_groups`` for ``nk`` checkpoint groups:
+    B * NH * nk * (G + 1) slots of 16384 + 256 bytes"""
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(load_library().ttt_hip_linear_backward_parts_slots(ctypes.byref(d), int(nk)))
+
+
+def linear_backward_parts_carry(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of ``ln_carry``: B * NH * 8 * lanes * 4, lanes = 64 at mini-batches of 16, 256 at mini-batches of 64"""
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(load_library().ttt_hip_linear_backward_parts_carry(ctypes.byref(d)))
+
+
+def ttt_linear_recompute_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
+                                grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
+                                grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
+                                grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots):
+    """Re-run the checkpoint groups [k0, k0 + nk) of the sequence the (whole-sequence) tensors describe from their checkpoints and
+    leave the state entering every step, and the state ending each group, in ``slots`` (``linear_backward_parts_slots`` bytes for
+    nk groups) - ``ttt_hip_linear_recompute_groups``, include/ttt_hip_bwd_parts.h.  The tensor list of ``ttt_linear_backward_impl``;
+    only XK, XV, last_eta, the LayerNorm parameters and the checkpoints are needed, the rest may be None.  MFMA sweep only."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
+               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
+               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(LIN_BWD_FIELDS) - _LIN_RECOMPUTE_FIELDS)
+    lib = load_library()
+    _device_bytes(slots, "slots")                 # (its size is the library's check: it knows whether the range is one)
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_linear_recompute_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                                 slots.numel() * slots.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    linear_bwd_parts_calls["recompute"] += 1
+
+
+def ttt_linear_sweep_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
+                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
+                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
+                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, ln_carry):
+    """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` ``ttt_linear_recompute_groups`` left for the
+    same range (``ttt_hip_linear_sweep_groups``).  Carries dW1 / db1 from ``grad_L_W1_last`` / ``grad_L_b1_last`` to ``grad_L_W1_init``
+    / ``grad_L_b1_init`` (which may be the same tensors) and the LayerNorm gradients' partial sums in ``ln_carry``
+    (``linear_backward_parts_carry`` bytes, fp32); the range with k0 == 0 also writes ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from
+    the last range to the first, the results are the bits of ``ttt_linear_backward_impl``.  The checkpoints and ``*_init_group`` may be
+    None.  The caller orders a recompute before the sweep of its slots (same stream, or events)."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
+               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
+               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, _LIN_SWEEP_UNUSED)
+    lib = load_library()
+    _device_bytes(slots, "slots")
+    _device_bytes(ln_carry, "ln_carry")
+    if ln_carry.dtype != torch.float32:
+        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_linear_sweep_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                             slots.numel() * slots.element_size(), _p(ln_carry),
+                                             ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    linear_bwd_parts_calls["sweep"] += 1
 
 
 # ------------------------------------------------------------------------------------------------

@@ -28,12 +28,67 @@ def _cs64_impl_default():
     return v
 
 
+def _backward_parts_default():
+    v = os.environ.get("TTT_LINEAR_BACKWARD_PARTS", "0")
+    if not v.isdigit():
+        raise ValueError(f"TTT_LINEAR_BACKWARD_PARTS: expected a non-negative integer (checkpoint groups per part, 0 = off), got {v!r}")
+    return int(v)
+
+
+def backward_in_parts(ext, impl, gpp, tensors, G):
+    """``ttt_linear_backward`` as ranges of ``gpp`` checkpoint groups, walked from the last range to the first (the entries of
+    include/ttt_hip_bwd_parts.h).  ``tensors``: the 21 of ``ttt_linear_backward`` - the ``*_init_group`` scratch is not used; dW1 / db1 are
+    carried IN PLACE in the output buffers, which start as copies of the upstream gradients of the final state (zeros in
+    ``HipLinear.backward``).  The recompute of the range to be swept next runs on ``pipeline.side_stream`` into one of two slot
+    workspaces while the caller's stream sweeps the current range; events order a sweep behind its recompute and a recompute behind
+    the sweep that last read its workspace; the side stream is joined into the caller's stream before this returns."""
+    from ttt_amd.models.ssm.pipeline import side_stream
+    (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, uW1, ub1, dOut, _, _, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV) = tensors
+    B, NH, NC, CS, F = XQ.shape
+    K = math.ceil(NC / G)
+    dev = XQ.device
+    ranges = [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]       # (k0, nk), the last range first
+    nbytes = ext.linear_backward_parts_slots(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl)
+    slots = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+    carry = torch.empty(ext.linear_backward_parts_carry(B, NH, NC, CS, F, G, XQ.dtype, impl=impl) // 4, dtype=_F32, device=dev)
+    dW1.copy_(uW1); db1.copy_(ub1)
+    main, side = torch.cuda.current_stream(dev), side_stream(dev)
+    rec_args = (None, XK, XV, last_eta, ln_w, ln_b, W1c, b1c) + (None,) * 13
+    sweep_args = (XQ, XK, XV, last_eta, ln_w, ln_b, None, None, dW1, db1, dOut, None, None, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
+    ready = [torch.cuda.Event() for _ in ranges]        # recompute of range n is done
+    swept = [torch.cuda.Event() for _ in ranges]        # sweep of range n is done: its workspace may be reused
+
+    def recompute(n):
+        with torch.cuda.stream(side):
+            if n >= 2:
+                side.wait_event(swept[n - 2])
+            ext.ttt_linear_recompute_groups(impl, *rec_args, G, *ranges[n], slots[n & 1])
+            ready[n].record(side)
+
+    side.wait_stream(main)                              # the inputs, the checkpoints and the workspaces are the caller's stream's
+    for t in slots:
+        t.record_stream(side)
+    recompute(0)
+    for n, (k0, nk) in enumerate(ranges):
+        if n + 1 < len(ranges):
+            recompute(n + 1)
+        main.wait_event(ready[n])
+        ext.ttt_linear_sweep_groups(impl, *sweep_args, G, k0, nk, slots[n & 1], carry)
+        swept[n].record(main)
+    main.wait_stream(side)
+
+
 class HipLinear(torch.autograd.Function):
     sharded_mode = False
     # Kernels of the calls at mini-batches of 64 with bf16 activations and head_dim 64: "auto" = what the library's selector picks
     # (the generic fp32-arithmetic kernels), "mfma" = the opt-in MFMA scan and sweep (csrc/ttt_lin64_body.h).  Every other call
     # is untouched.  Default from the environment variable TTT_LINEAR_CS64_IMPL, read once at import.
     cs64_impl = _cs64_impl_default()
+    # The backward in parts: 0 = one call (default), n > 0 = ranges of n checkpoint groups, the recompute of the next range on the
+    # pipeline's side stream beside the reverse walk of the current one (``backward_in_parts``) - where the call runs the MFMA sweep,
+    # has at least two ranges and the extension has the entries; every other call is the one call.  Same bits either way.  Default
+    # from the environment variable TTT_LINEAR_BACKWARD_PARTS, read once at import.
+    backward_parts = _backward_parts_default()
 
     @staticmethod
     def _impl(CS, F, act):
@@ -42,6 +97,16 @@ class HipLinear(torch.autograd.Function):
         if HipLinear.cs64_impl not in ("auto", "mfma"):
             raise ValueError(f"HipLinear.cs64_impl: expected 'auto' or 'mfma', got {HipLinear.cs64_impl!r}")
         return None
+
+    @staticmethod
+    def _in_parts(ext, impl, XQ, G):
+        gpp = HipLinear.backward_parts
+        if not isinstance(gpp, int) or gpp < 0:
+            raise ValueError(f"HipLinear.backward_parts: expected a non-negative integer, got {gpp!r}")
+        B, NH, NC, CS, F = XQ.shape
+        if gpp == 0 or math.ceil(NC / G) <= gpp or not hasattr(ext, "ttt_linear_sweep_groups"):
+            return False
+        return ext.resolved_impl(B, NH, NC, CS, F, G, XQ.dtype, mlp=False, backward=True, impl=impl) == "mfma"
 
     @staticmethod
     def forward(ctx, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, XQ_batch, XV_batch, XK_batch, eta_batch,
@@ -88,9 +153,13 @@ class HipLinear(torch.autograd.Function):
         dW1, db1 = e32(B, NH, F, F), e32(B, NH, 1, F)
         d_eta = torch.empty(B, NH, NC, CS, 1, device=dev, dtype=act)
         dQ, dK, dV = (torch.empty_like(XQ) for _ in range(3))
-        bwd = ext.ttt_linear_backward if ctx.impl is None else (lambda *a: ext.ttt_linear_backward_impl(ctx.impl, *a))
-        bwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
-            d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV, G)
+        tensors = (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
+                   d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
+        if HipLinear._in_parts(ext, ctx.impl, XQ, G):
+            backward_in_parts(ext, ctx.impl, int(HipLinear.backward_parts), tensors, G)
+        else:
+            bwd = ext.ttt_linear_backward if ctx.impl is None else (lambda *a: ext.ttt_linear_backward_impl(ctx.impl, *a))
+            bwd(*tensors, G)
         ln_dt, st_dt = ctx.param_dtypes
         row = d_eta.transpose(-2, -1)
         rows = ctx.eta_shape[-2]

@@ -53,15 +53,18 @@ extern "C" {
  *    after 2 s, poisons its outputs with NaN and sets the sticky error that ttt_hip_sweep_error_clear() acknowledges (return code -3
  *    of the next call), like the backward's cluster.  Signatures unchanged.
  *    (Still 5: TTT-Linear at CS=64 gained MFMA kernels that run on an explicit TTT_IMPL_MFMA only - a request that used to be refused
- *    with -1; what TTT_IMPL_AUTO resolves to, every signature and every tensor contract are unchanged.) */
+ *    with -1; what TTT_IMPL_AUTO resolves to, every signature and every tensor contract are unchanged.)
+ *    (Still 5: the TTT-MLP backward at CS=16 gained an MFMA kernel that runs on an explicit TTT_IMPL_MFMA only - a request that used
+ *    to be refused with -1.  It keeps its per-step state in the four *_init_group buffers (required, as for the generic kernels) and
+ *    asks for no workspace; what TTT_IMPL_AUTO resolves to, every signature and every tensor contract are unchanged.) */
 #define TTT_HIP_ABI_VERSION 5
 
 enum { TTT_DTYPE_BF16 = 0, TTT_DTYPE_F32 = 1 };
 /* implementation selector: AUTO picks the MFMA kernels when the geometry is supported - bf16, F=64 and
  * TTT-MLP forward/backward at CS=64, TTT-MLP forward at CS=16, TTT-Linear forward/backward at CS=16 -
  * and the generic fp32-arithmetic kernels otherwise; TTT_IMPL_MFMA makes an unsupported geometry an error.
- * TTT-Linear forward/backward at CS=64 on explicit TTT_IMPL_MFMA: the MFMA kernels of that geometry are opt-in, AUTO keeps
- * resolving it to the generic kernels. */
+ * TTT-Linear forward/backward at CS=64 and TTT-MLP backward at CS=16 on explicit TTT_IMPL_MFMA: the MFMA kernels of those calls are
+ * opt-in, AUTO keeps resolving them to the generic kernels. */
 enum { TTT_IMPL_AUTO = 0, TTT_IMPL_GENERIC = 1, TTT_IMPL_MFMA = 2 };
 
 typedef struct ttt_dims {
@@ -98,8 +101,9 @@ typedef struct ttt_mlp_bwd_args {
     const float* W2_checkpoints; const float* b2_checkpoints;
     const void*  XQW;            /* forward output (unused by the arithmetic; kept for ABI parity) */
     /* caller-allocated re-materialisation scratch, [B,NH,G,...] (mlp_tk.py:192-210).  The generic kernels keep their per-step
-     * state in the four *_init_group buffers (required there); the MFMA backward works in `ws` only and accepts NULL for all
-     * sixteen; the twelve below are never touched by this implementation. */
+     * state in the four *_init_group buffers (required there), and so does the MFMA backward at CS=16 (fp32 states in this layout);
+     * the MFMA backward at CS=64 works in `ws` only and accepts NULL for all sixteen; the twelve below are never touched by this
+     * implementation. */
     float* W1_init_group; float* b1_init_group; float* W2_init_group; float* b2_init_group;
     void*  x_hat_ln_group;          /* bf16 [B,NH,G,CS,F]  */
     float* std_ln_group;            /* f32  [B,NH,G,CS,1]  */

@@ -31,8 +31,9 @@ static int check_dims(const ttt_dims* d) {
 static int resolve(const ttt_dims* d, bool mlp, bool bwd) {
     if (d->impl == TTT_IMPL_GENERIC) return ttt::generic::supports(d) ? TTT_IMPL_GENERIC : -1;
     if (d->impl == TTT_IMPL_MFMA) return ttt::mfma::supports(d, mlp, bwd) ? TTT_IMPL_MFMA : -1;
-    // TTT-Linear at CS = 64: the MFMA kernels are opt-in (explicit TTT_IMPL_MFMA above); AUTO stays on the generic kernels
-    if (ttt::mfma::supports(d, mlp, bwd) && (mlp || d->CS != 64)) return TTT_IMPL_MFMA;
+    // TTT-Linear at CS = 64 and the TTT-MLP backward at CS = 16: the MFMA kernels are opt-in (explicit TTT_IMPL_MFMA above); AUTO
+    // stays on the generic kernels
+    if (ttt::mfma::supports(d, mlp, bwd) && (mlp || d->CS != 64) && !(mlp && bwd && d->CS == 16)) return TTT_IMPL_MFMA;
     if (ttt::generic::supports(d)) return TTT_IMPL_GENERIC;
     return -1;
 }
@@ -201,9 +202,10 @@ int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws,
     if (r < 0) return fail("ttt_hip: mlp_backward: unsupported geometry/dtype for the requested impl");
     if (wsb < ws_bytes(d, true, true) || (ws_bytes(d, true, true) && !ws)) return fail("ttt_hip: mlp_backward: workspace too small");
     if (check_sweep_error("mlp_backward")) return -3;
-    // the caller-allocated re-materialisation scratch of the reference contract: only the generic kernels keep their per-step
-    // state in the four *_init_group buffers; the MFMA backward works in `ws` and accepts NULL for all sixteen
-    if (r != TTT_IMPL_MFMA) { NEED(W1_init_group); NEED(b1_init_group); NEED(W2_init_group); NEED(b2_init_group); }
+    // the caller-allocated re-materialisation scratch of the reference contract: the generic kernels and the MFMA backward at
+    // mini-batches of 16 keep their per-step state in the four *_init_group buffers; the MFMA backward at 64 works in `ws` and
+    // accepts NULL for all sixteen
+    if (r != TTT_IMPL_MFMA || d->CS == 16) { NEED(W1_init_group); NEED(b1_init_group); NEED(W2_init_group); NEED(b2_init_group); }
     if (r == TTT_IMPL_MFMA) {
         const int rc = ttt::mfma::mlp_backward(d, a, ws, (hipStream_t)stream);
         if (rc == -10) return fail("ttt_hip: mlp_backward: the MFMA backward needs at least 4 visible compute units (four co-resident workgroups per (b,h))");

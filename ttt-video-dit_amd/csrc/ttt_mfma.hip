@@ -2,6 +2,7 @@
 //   TTT-MLP forward   CS = 64: ttt_mfma2.hip (8-wave register-resident scan)   CS = 16: ttt_mfma16.hip
 //   TTT-MLP backward  CS = 64: revision 4 - ttt_mfma_rc4.hip (group recompute), ttt_mfma_bwd4.hip (cluster sweep with deriver
 //                     waves, tail), orchestrated by ttt_mfma_bwd2.hip
+//                     CS = 16 (explicit TTT_IMPL_MFMA only): ttt_mlp16_bwd_body.h, one kernel in ttt_mfma16.hip
 //   TTT-Linear forward / backward at CS = 16: ttt_mfma16.hip ; at CS = 64 (explicit TTT_IMPL_MFMA only): ttt_lin64_body.h, same file
 // (Round 1's 4-wave scan / recompute kernel lived here; its last user, revision 3 of the backward, lost its round-3 A/B against
 // revision 4 - 17.8 vs 13.4 ms per backward at NC = 804, profiles/r3h_* - and was removed with it.)
@@ -19,7 +20,8 @@ unsigned long long* get_debug_timing() { return g_dbg; }
 
 bool supports(const ttt_dims* d, bool mlp, bool backward) {
     if (!(d->F == 64 && d->act_dtype == TTT_DTYPE_BF16)) return false;
-    if (d->CS == 16) return !backward || !mlp;  // mini-batches of 16 (ttt_mfma16.hip): MLP forward, Linear forward + backward
+    // mini-batches of 16 (ttt_mfma16.hip): MLP and Linear, forward and backward; capi.hip keeps AUTO on the generic MLP backward
+    if (d->CS == 16) return true;
     if (!mlp) return d->CS == 64;                // TTT-Linear at 64 (ttt_lin64_body.h); capi.hip keeps AUTO on the generic kernels
     return d->CS == 64 && (!backward || bwd_available());
 }
@@ -34,6 +36,21 @@ void mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, hipStre
     p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
     if (d->CS == 16) launch_scan_forward_cs16(p, d->B * d->NH, g_dbg, s);
     else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
+}
+// TTT-MLP backward at CS = 16: the per-step state lives in the caller's four *_init_group buffers, nothing in `ws`
+void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t s) {
+    wv::Mlp16BwdParams p = {};
+    p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
+    p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
+    p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints; p.W2c = a->W2_checkpoints; p.b2c = a->b2_checkpoints;
+    p.dOut = (const __bf16*)a->grad_L_XQW;
+    p.dW1_last = a->grad_L_W1_last; p.db1_last = a->grad_L_b1_last; p.dW2_last = a->grad_L_W2_last; p.db2_last = a->grad_L_b2_last;
+    p.W1s = a->W1_init_group; p.b1s = a->b1_init_group; p.W2s = a->W2_init_group; p.b2s = a->b2_init_group;
+    p.dln_w = a->grad_L_ttt_norm_weight; p.dln_b = a->grad_L_ttt_norm_bias;
+    p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init; p.dW2 = a->grad_L_W2_init; p.db2 = a->grad_L_b2_init;
+    p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
+    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    launch_mlp_backward_cs16(p, d->B * d->NH, s);
 }
 // steps [step0, step0 + nsteps) of the scan: the same kernel over a part of the sequence, started from the state in
 // a->*_init (what the previous part left in *_final), its checkpoints written at their places in the whole sequence's arrays.

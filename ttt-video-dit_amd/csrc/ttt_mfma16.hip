@@ -40,6 +40,7 @@
 #include "ttt_lin16_body.h"
 #include "ttt_lin64_body.h"
 #include "ttt_mlp16_body.h"
+#include "ttt_mlp16_bwd_body.h"
 #include "once_per_device.h"
 
 namespace ttt {
@@ -153,6 +154,15 @@ __global__ __launch_bounds__(NT16) void mlp_scan16_body_kernel(wv::Mlp16ChunkPar
     mlp16::forward_part(bk, c, blockIdx.x);
 }
 
+// TTT-MLP backward at mini-batches of 16 (ttt_mlp16_bwd_body.h): one workgroup of eight waves per (b, h), each owning a slice of 32 hidden
+// units as in the forward, walks the checkpoint groups from the last to the first: recompute into the caller's *_init_group slots, then
+// the reverse walk.  Explicit TTT_IMPL_MFMA only (capi.hip).
+__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_bwd16_kernel(wv::Mlp16BwdParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    mlp16::bwd::backward(bk, p, blockIdx.x);
+}
+
 // backward: one wave per workgroup (48 .. 96 scans on 256 CUs: a CU of its own per scan; up to 512 registers per lane)
 __global__ __launch_bounds__(64) void linear_bwd16_kernel(wv::Lin16Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -264,6 +274,14 @@ void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*
     const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
     const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
     hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, c);
+}
+
+void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s) {
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::mlp_bwd16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
+    });
+    hipLaunchKernelGGL(v16::mlp_bwd16_kernel, dim3(n_bh), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, p);
 }
 
 }  // namespace mfma

@@ -91,6 +91,7 @@ static size_t align128(size_t v) { return (v + 127) & ~(size_t)127; }
 size_t workspace_bytes(const ttt_dims* d, bool mlp, bool backward) {
     if (mlp && !backward && d->CS == 64) return scan_pair_workspace_bytes(d->B * d->NH);     // the pair scan's ring + flag lines
     if (!mlp || !backward) return 0;
+    if (d->CS == 16) return 0;                        // the CS = 16 backward keeps its per-step state in the four *_init_group buffers
     const size_t nbh = (size_t)d->B * d->NH;
     const size_t slots = (size_t)groups_per_chunk(d) * d->G + 1;
     // two record buffers + carried state gradient + exchange records and flag lines of the cluster sweep + the state after the
@@ -291,6 +292,7 @@ static int mlp_backward4(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws,
 }
 
 int mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, hipStream_t s) {
+    if (d->CS == 16) { mlp_backward_cs16(d, a, s); return 0; }      // one workgroup per (b,h): no cluster, no hand-over
     const int nbh = d->B * d->NH, G = d->G, NC = d->NC;
     const int per_launch = sweep_clusters_per_launch();
     if (per_launch < 1) return -10;      // fewer than 4 compute units visible: the cluster sweep cannot be co-resident

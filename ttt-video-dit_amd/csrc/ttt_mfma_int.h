@@ -34,6 +34,7 @@ static_assert(offsetof(ScanParams, eps) == offsetof(wv::Mlp16Params, eps) && off
               "ScanParams and wv::Mlp16Params list the same leading fields");
 
 bool bwd_available();
+void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t s);       // ttt_mfma.hip
 int groups_per_chunk(const ttt_dims* d);
 // revision-2 forward scan (ttt_mfma2.hip): 8 waves per (b,h), VGPR-form MFMA, LDS transposed reads
 // `ws`: the caller's forward workspace (scan_pair_workspace_bytes) or null; with it, the scan runs as a PAIR of workgroups per (b,h)
@@ -46,6 +47,7 @@ int device_cu_count();                // compute units of the current device (ca
 int get_debug_fast_records();
 // mini-batches of 16 tokens, forward only (ttt_mfma16.hip): the evaluation / sampling geometry
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long* dbg, hipStream_t s);
+void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s);       // TTT-MLP backward, one 8-wave workgroup per (b,h)
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h); whole sequence or a part
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h); whole sequence or a part

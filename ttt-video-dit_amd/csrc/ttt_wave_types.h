@@ -81,5 +81,20 @@ struct Mlp16ChunkParams {
     float *W1f, *b1f, *W2f, *b2f;
 };
 
+// arguments of the TTT-MLP backward at mini-batches of 16 tokens (ttt_mlp16_bwd_body.h)
+struct Mlp16BwdParams {
+    const __bf16 *XQ, *XK, *XV, *eta;       // [B,NH,NC,16,64] x3, [B,NH,NC,16,1]
+    const float *ln_w, *ln_b;               // [NH,64]
+    const float *W1c, *b1c, *W2c, *b2c;     // checkpoints [B,NH,K,...] (read only)
+    const __bf16* dOut;                     // [B,NH,NC,16,64]
+    const float *dW1_last, *db1_last, *dW2_last, *db2_last;      // upstream gradient of the final state
+    float *W1s, *b1s, *W2s, *b2s;           // the four *_init_group buffers [B,NH,G,64,256], [B,NH,G,1,256], [B,NH,G,256,64], [B,NH,G,1,64]
+    float *dln_w, *dln_b;                   // [B,NH,1,64]
+    float *dW1, *db1, *dW2, *db2;           // gradient of the initial state (carried here between the groups of the call)
+    __bf16 *deta, *dXQ, *dXK, *dXV;
+    int NH, NC, G, K;
+    float eps;
+};
+
 }  // namespace wv
 }  // namespace ttt

@@ -432,6 +432,25 @@ def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkp
                  grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
                  grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
     """TTT-MLP backward; the 42 tensors + 1 int of the reference call site mlp_tk.py:227-275."""
+    ttt_backward_impl(None, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+                      b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+                      std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+                      x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+                      grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+                      grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+                      grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size)
+
+
+def ttt_backward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+                      b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+                      std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+                      x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+                      grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+                      grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+                      grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size):
+    """``ttt_backward`` with the selector of THIS call: ``impl`` None (the global selector) or 'auto' / 'generic' / 'mfma' - 'mfma' at
+    mini-batches of 16 runs the opt-in MFMA backward of csrc/ttt_mlp16_bwd_body.h, which keeps its per-step state in the four
+    ``*_init_group`` buffers (required there, as for the generic kernels).  (A function of its own, as ``ttt_linear_backward_impl``.)"""
     tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
                b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
                std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
@@ -439,7 +458,7 @@ def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkp
                grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
                grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
                grad_L_XQ, grad_L_XK, grad_L_XV)
-    _launch("ttt_hip_mlp_backward", *_scan_args(_MlpBwd, _MLP_BWD_SPEC, tensors, checkpoint_group_size, optional=_MLP_BWD_SCRATCH))
+    _launch("ttt_hip_mlp_backward", *_scan_args(_MlpBwd, _MLP_BWD_SPEC, tensors, checkpoint_group_size, optional=_MLP_BWD_SCRATCH, impl=impl))
 
 
 def ttt_linear_forward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,

@@ -201,7 +201,11 @@ class FusedPreScanMLP(torch.autograd.Function):
         # the reference's sixteen caller-allocated re-materialisation buffers (mlp_tk.py:192-210): the MFMA backward touches none
         # of them (0.55 GB per call at 48 heads that nobody reads - round-3 verdict), the generic kernels four; the reference-
         # shaped wrapper (mlp_tk.py here) keeps allocating all of them, as the ABI it mirrors demands
-        if ext.resolved_impl(B, NH, NC, CS, Fh, G, _BF16, mlp=True, backward=True) == "generic":
+        # (the MFMA backward at mini-batches of 16 - TkMLP.cs16_bwd_impl - keeps its per-step state in those four too)
+        from ttt_amd.models.ssm.mlp_tk import TkMLP
+        impl = TkMLP.bwd_impl(CS, Fh, _BF16)
+        resolved = ext.resolved_impl(B, NH, NC, CS, Fh, G, _BF16, mlp=True, backward=True, impl=impl)
+        if resolved == "generic" or (resolved == "mfma" and CS == 16):
             remat = (e32(B, NH, G, Fh, H), e32(B, NH, G, 1, H), e32(B, NH, G, H, Fh), e32(B, NH, G, 1, Fh)) + (None,) * 12
         else:
             remat = (None,) * 16
@@ -210,8 +214,8 @@ class FusedPreScanMLP(torch.autograd.Function):
         d_eta = torch.empty(B, NH, NC, CS, 1, device=dev, dtype=_BF16)
         dQ, dK, dV = (torch.empty(B, NH, NC, CS, Fh, device=dev, dtype=_BF16) for _ in range(3))
         lw, lb = w32.reshape(1, NH, 1, Fh), b32.reshape(1, NH, 1, Fh)
-        ext.ttt_backward(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, W1c, b1c, W2c, b2c, g_out, *remat, *up, g_out,
-                         d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
+        TkMLP.bwd_call(ext, impl)(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, W1c, b1c, W2c, b2c, g_out, *remat, *up, g_out,
+                                  d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
         del XQ, XK, XV
         # pre backward (re-uses the raw projections)
         flat = lambda t: t.view(B, NH, L, Fh)

@@ -13,11 +13,20 @@ Differences from the reference wrapper, on purpose:
 """
 from __future__ import annotations
 
+import functools
 import math
+import os
 
 import torch
 
 _BF16, _F32 = torch.bfloat16, torch.float32
+CS16_BWD_IMPLS = ("auto", "mfma")
+
+
+def _check_cs16_bwd_impl(value):
+    if value not in CS16_BWD_IMPLS:
+        raise ValueError(f"TkMLP.cs16_bwd_impl / TTT_MLP_CS16_BWD_IMPL: expected 'auto' or 'mfma', got {value!r}")
+    return value
 
 
 def _ext():
@@ -32,6 +41,21 @@ def _last_row(eta: torch.Tensor, act_dtype) -> torch.Tensor:
 
 class TkMLP(torch.autograd.Function):
     sharded_mode = False  # head-sharded tensor parallel (next row): op is head-local
+    # the backward at mini-batches of 16 (head dim 64, bf16): "auto" - what the library resolves, the generic kernels - or "mfma" -
+    # the opt-in MFMA backward of csrc/ttt_mlp16_bwd_body.h.  Read by this backward and by FusedPreScanMLP's; ignored at every
+    # other geometry (like HipLinear._impl).  The forward call is not affected.
+    cs16_bwd_impl = _check_cs16_bwd_impl(os.environ.get("TTT_MLP_CS16_BWD_IMPL", "auto"))
+
+    @staticmethod
+    def bwd_impl(CS, F, act_dtype):
+        """the ``impl`` of ``ttt_backward_impl`` for a backward at this geometry: None (the global selector) unless the switch applies"""
+        value = _check_cs16_bwd_impl(TkMLP.cs16_bwd_impl)
+        return "mfma" if value == "mfma" and CS == 16 and F == 64 and act_dtype == _BF16 else None
+
+    @staticmethod
+    def bwd_call(ext, impl):
+        """the binding's backward for that ``impl``: ``ttt_backward`` itself unless the switch applies"""
+        return ext.ttt_backward if impl is None else functools.partial(ext.ttt_backward_impl, impl)
 
     @staticmethod
     def forward(ctx, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
@@ -85,8 +109,8 @@ class TkMLP(torch.autograd.Function):
         d_eta = torch.empty(B, NH, NC, CS, 1, device=dev, dtype=_BF16)
         dQ, dK, dV = (torch.empty_like(XQ) for _ in range(3))
 
-        ext.ttt_backward(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c, out, *remat, *up, g_out,
-                         d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
+        TkMLP.bwd_call(ext, TkMLP.bwd_impl(CS, F, XQ.dtype))(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c, out, *remat, *up,
+                                                              g_out, d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
 
         ln_dt, st_dt = ctx.param_dtypes
         d_lnw = d_lnw.sum(dim=0).squeeze(1).to(ln_dt)

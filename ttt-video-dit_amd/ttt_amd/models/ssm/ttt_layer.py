@@ -411,7 +411,7 @@ class TTTBase(nn.Module):
         CS = self.mini_batch_size
         if n < 2 or heads_only or not isinstance(self, TTTMLP) or CS not in (64, 16) or remat_cache.replaying("scan"):
             return None
-        if CS == 16 and torch.is_grad_enabled():       # (the CS = 16 scan has no MFMA backward: with grad enabled the layer stays one piece)
+        if CS == 16 and torch.is_grad_enabled():       # (the MFMA backward of the CS = 16 scan is opt-in - TkMLP.cs16_bwd_impl - and unmeasured inside a step: with grad enabled the layer stays one piece)
             return None
         if not linear3_applies(self.wq, self.wk, self.wv, x) or not linear3_applies(self.wo, self.wo, self.wo, x):
             return None                    # (DTensor parameters, autocast: the pre-pass's raw GEMMs would not be the modules' arithmetic)

@@ -1,6 +1,6 @@
 """Sampling-path measurement ("Sampling (cfg 5): latent frames/s"; 8f #3) on one MI355X.
 
-    python tools/sample_bench.py [--video-length 3sec] [--steps 3] [--layers 42] [--sequential] [--pipeline-parts N] [--ab ROUNDS]
+    python tools/sample_bench.py [--video-length 3sec] [--steps 3] [--layers 42] [--sequential] [--pipeline-parts N] [--ab ROUNDS] [--ab-pair ROUNDS]
 
 CogVideoX-5B + TTT-MLP in bf16 with the evaluation settings of the reference (configs/eval/ttt-mlp/*.toml:
 mini_batch_size = 16, no scan checkpoints), random-init weights and synthetic text embeddings, driven by the mirrored
@@ -40,6 +40,9 @@ def main():
                     help="TTT layer forward as a pipeline over exactly N parts of the sequence; 0 = one piece (default: the library's plan)")
     ap.add_argument("--ab", type=int, default=0, metavar="ROUNDS",
                     help="alternate one piece / the default plan inside this process, ROUNDS timed runs of --steps steps each")
+    ap.add_argument("--ab-pair", type=int, default=0, metavar="ROUNDS",
+                    help="alternate the default plan with TTTBase.cs16_scan_pair off / on (the CS = 16 scan as pairs of workgroups) inside this "
+                         "process, ROUNDS timed runs of --steps steps each")
     a = ap.parse_args()
 
     import test_time_training as ext
@@ -111,15 +114,19 @@ def main():
         torch.cuda.synchronize()
         return out
 
-    if a.ab:
-        arms = {"one_piece": 0, "default": None}
+    if a.ab or a.ab_pair:
+        # arm: (parts, TTTBase.cs16_scan_pair); the second arm's time minus the first's is reported
+        arms = {"one_piece": (0, 0), "default": (None, 0)} if a.ab else {"default": (None, 0), "default_pair": (None, 1)}
+        first, second = list(arms)
         times = {k: [] for k in arms}
-        for k, n in arms.items():                            # warm-up of both arms: GEMM selection per shape, allocator
+        for k, (n, pair) in arms.items():                    # warm-up of both arms: GEMM selection per shape, allocator
             set_parts(n)
+            TTTBase.cs16_scan_pair = pair
             run(1)
-        for _ in range(a.ab):
-            for k, n in arms.items():
+        for _ in range(a.ab or a.ab_pair):
+            for k, (n, pair) in arms.items():
                 set_parts(n)
+                TTTBase.cs16_scan_pair = pair
                 t0 = time.perf_counter()
                 out = run(a.steps)
                 times[k].append(round((time.perf_counter() - t0) / a.steps, 4))
@@ -127,8 +134,8 @@ def main():
         med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
         if rank == 0:
             print(json.dumps({"metric": "sampling_denoising_step_seconds_ab", "unit": "s/step (cond+uncond)", "median": med, "runs": times,
-                              "one_piece_spread": round(max(times["one_piece"]) - min(times["one_piece"]), 4),
-                              "default_minus_one_piece": round(med["default"] - med["one_piece"], 4),
+                              f"{first}_spread": round(max(times[first]) - min(times[first]), 4),
+                              f"{second}_minus_{first}": round(med[second] - med[first], 4), "hand_over_error": ext.sweep_error(),
                               "config": {"video_length": a.video_length, "layers": cfg.num_layers, "steps_per_run": a.steps, "tokens": L,
                                          "mini_batches": NC, "scan_impl": impl},
                               "peak_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}))

@@ -97,7 +97,7 @@ def scan_only(a, ext, layer, meta, x, L, parts, set_parts, res):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parts", default="0,2,3,4")
+    ap.add_argument("--parts", default="0,2,3,4", help='variants: N parts, "default", each optionally with "+pair" (the CS = 16 pair scan on)')
     ap.add_argument("--video-length", default="9sec")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mini-batch", type=int, default=64, choices=[64, 16], help="16: the evaluation settings (no scan checkpoints)")
@@ -146,7 +146,8 @@ def main():
     x = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16().requires_grad_(not a.no_grad)
     dy = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16() * 0.1
     params = [p for p in layer.parameters() if p.requires_grad]
-    parts = [v if v == "default" else int(v) for v in a.parts.split(",")]
+    # a variant: a number of parts or "default", with "+pair" behind it = TTTBase.cs16_scan_pair on for that variant (CS = 16)
+    parts = [v if (v == "default" or v.endswith("+pair")) else int(v) for v in a.parts.split(",")]
     res = {"L": L, "batch": a.batch, "mini_batch": a.mini_batch, "ssm": a.ssm, "tuned_gemms": bool(tuned), "by_parts": {}}
     if linear:
         res["cs64_impl"] = HipLinear.cs64_impl
@@ -154,6 +155,11 @@ def main():
     default_linear = layer.ttt.linear_pipeline_parts
 
     def set_parts(n):
+        from ttt_amd.models.ssm.ttt_layer import TTTBase
+        pair = isinstance(n, str) and n.endswith("+pair")
+        TTTBase.cs16_scan_pair = int(pair)
+        if pair:
+            n = n[:-5] if n[:-5] == "default" else int(n[:-5])
         if linear:
             layer.ttt.linear_pipeline_parts = default_linear if n == "default" else n
         elif n == "default":

@@ -5,6 +5,7 @@
 #include <string.h>
 #include "../../include/ttt_hip_parts.h"
 #include "../../include/ttt_hip_bwd_parts.h"
+#include "../../include/ttt_hip_pair16.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -188,6 +189,32 @@ int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int 
     void* use_ws = (ws && wsb >= ws_bytes(d, true, false)) ? ws : nullptr;
     ttt::mfma::mlp_forward_chunk(d, a, step0, nsteps, W1_final, b1_final, W2_final, b2_final, use_ws, (hipStream_t)stream);
     return post_launch("mlp_forward_chunk");
+}
+
+// include/ttt_hip_pair16.h
+static bool pair16_serves(const ttt_dims* d) {
+    return d->act_dtype == TTT_DTYPE_BF16 && d->F == 64 && d->CS == 16 && resolve(d, true, false) == TTT_IMPL_MFMA;
+}
+size_t ttt_hip_mlp_forward_pair16_workspace(const ttt_dims* d) {
+    if (check_dims(d) || !pair16_serves(d)) return 0;
+    return ttt::mfma::scan_pair16_workspace_bytes(d->B * d->NH);
+}
+int ttt_hip_mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
+                                     float* W2_final, float* b2_final, void* ws, size_t wsb, void* stream) {
+    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
+    if (!pair16_serves(d))
+        return fail("ttt_hip: mlp_forward_chunk_pair16: the pair scan serves bf16 activations, F = 64, mini-batches of 16 on the MFMA scan only");
+    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
+        return fail("ttt_hip: mlp_forward_chunk_pair16: the part [step0, step0 + nsteps) must lie inside [0, NC)");
+    if ((W1_final || b1_final || W2_final || b2_final) && !(W1_final && b1_final && W2_final && b2_final))
+        return fail("ttt_hip: mlp_forward_chunk_pair16: give all four final-state buffers or none");
+    if (!ws || wsb < ttt::mfma::scan_pair16_workspace_bytes(d->B * d->NH))
+        return fail("ttt_hip: mlp_forward_chunk_pair16: workspace null or smaller than ttt_hip_mlp_forward_pair16_workspace(d)");
+    if (check_sweep_error("mlp_forward_chunk_pair16")) return -3;
+    const int rc = ttt::mfma::mlp_forward_chunk_pair16(d, a, step0, nsteps, W1_final, b1_final, W2_final, b2_final, ws, (hipStream_t)stream);
+    if (rc < 0) return fail("ttt_hip: mlp_forward_chunk_pair16: could not allocate the host-mapped error word");
+    const int pl = post_launch("mlp_forward_chunk_pair16");
+    return pl ? pl : rc;
 }
 
 int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, size_t wsb, void* stream) {

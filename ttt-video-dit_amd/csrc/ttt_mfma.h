@@ -13,6 +13,8 @@ void set_debug_dump(float* device_buffer);     // revision-2 forward: intermedia
 void mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, hipStream_t s);
 void mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, float* W2f, float* b2f,
                        void* ws, hipStream_t s);          // CS = 64 only; ws: the forward workspace or null (one workgroup per (b,h))
+int  mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, float* W2f, float* b2f,
+                              void* ws, hipStream_t s);   // CS = 16 as a pair of workgroups per (b,h): 0 pairs, 1 one workgroup, < 0 nothing launched
 int  mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, hipStream_t s);   // 0, or < 0: no kernel was launched
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* ws, hipStream_t s);
 void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f,

@@ -72,6 +72,20 @@ void mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, 
     if (cs16) launch_scan_forward_cs16(p, d->B * d->NH, g_dbg, s);
     else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
 }
+// the same part at CS = 16 as a pair of workgroups per (b, h) (ttt_mlp16_pair_body.h); `ws`: scan_pair16_workspace_bytes
+int mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, float* W2f,
+                             float* b2f, void* ws, hipStream_t s) {
+    ScanParams p = {};
+    p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
+    p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
+    p.W1 = a->W1_init; p.b1 = a->b1_init; p.W2 = a->W2_init; p.b2 = a->b2_init;
+    p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints; p.W2c = a->W2_checkpoints; p.b2c = a->b2_checkpoints;
+    p.out = (__bf16*)a->XQW;
+    p.NH = d->NH; p.NC = nsteps; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    p.NCs = d->NC; p.ck0 = step0;
+    p.W1f = W1f; p.b1f = b1f; p.W2f = W2f; p.b2f = b2f;
+    return launch_scan_forward_pair16(p, d->B * d->NH, ws, s);
+}
 // steps [step0, step0 + nsteps) of the TTT-Linear scan: the same kernel over a part of the sequence, started from the state in
 // a->W1_init / b1_init, its checkpoints written at their places in the whole sequence's arrays, the state after its last step
 // left in W1f / b1f (both null: not stored).  Parts start at any step at both mini-batch sizes (ttt_wave_types.h).

@@ -41,6 +41,7 @@
 #include "ttt_lin64_body.h"
 #include "ttt_mlp16_body.h"
 #include "ttt_mlp16_bwd_body.h"
+#include "ttt_mlp16_pair_body.h"
 #include "once_per_device.h"
 
 namespace ttt {
@@ -152,6 +153,62 @@ __global__ __launch_bounds__(NT16) void mlp_scan16_body_kernel(wv::Mlp16ChunkPar
     extern __shared__ __attribute__((aligned(16))) char smem[];
     DeviceWave bk{smem};
     mlp16::forward_part(bk, c, blockIdx.x);
+}
+
+// TTT-MLP forward scan at mini-batches of 16 as a PAIR of workgroups per (b, h) (ttt_mlp16_pair_body.h; opt-in): the device side of
+// the hand-over policy - cdna_hip_programming.md Guideline 16 form R1, as the CS = 64 pair scan (ttt_mfma2.hip).  Record payloads are
+// write-through (sc1) buffer stores, drained by every storing wave in front of the workgroup barrier that precedes the flag; ONE lane
+// stores the flag word (relaxed, agent scope); the consumer polls that word (bounded by the 100 MHz wall clock: 2 s) and reads the
+// payload with sc1 buffer loads only.
+struct Pair16Params {
+    char* ring;                       // [B NH][RING][REC_BYTES]
+    unsigned* flags;                  // [B NH][FLAG_WORDS], zeroed in front of every launch
+    unsigned* err;                    // host-mapped error word of the process
+    int nbh, nbh8;                    // workgroup b < nbh: role A of (b, h) = b ; b >= nbh8: role B of b - nbh8 (nbh8 % 8 == 0: same XCD)
+};
+struct DeviceHandover {
+    __amdgpu_buffer_rsrc_t rR;        // this (b, h)'s ring
+    unsigned* fl;                     // this (b, h)'s flag words
+    unsigned* err;
+    __device__ __forceinline__ DeviceHandover(const Pair16Params& q, int bh)
+        : rR(__builtin_amdgcn_make_buffer_rsrc(q.ring + (size_t)bh * mlp16::pair::RING * mlp16::pair::REC_BYTES, 0,
+                                               mlp16::pair::RING * mlp16::pair::REC_BYTES, 0x00020000)),
+          fl(q.flags + (size_t)bh * mlp16::pair::FLAG_WORDS), err(q.err) {}
+    __device__ __forceinline__ void store16(int voff, int soff, wv::u32x4 v) const { __builtin_amdgcn_raw_buffer_store_b128(v, rR, voff, soff, 16); }
+    __device__ __forceinline__ void store4(int voff, int soff, unsigned v) const { __builtin_amdgcn_raw_buffer_store_b32(v, rR, voff, soff, 16); }
+    __device__ __forceinline__ wv::u32x4 load16(int voff, int soff) const { return __builtin_amdgcn_raw_buffer_load_b128(rR, voff, soff, 16); }
+    __device__ __forceinline__ void drain() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+    __device__ __forceinline__ void post(int word, unsigned v) const { __hip_atomic_store(fl + word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ unsigned peek(int word) const {
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(fl + word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    __device__ __forceinline__ bool wait_ge(int word, unsigned need) const {
+        bool ok = true;
+        if (peek(word) < need) {
+            const unsigned long long t_poll = wall_clock64();
+            const unsigned long long t_lim = 200000000ull;                      // 2 s of the constant 100 MHz counter
+            unsigned spins = 0u;
+            do {
+                __builtin_amdgcn_s_sleep(1);
+                if ((++spins & 255u) == 0u && wall_clock64() - t_poll > t_lim) ok = false;
+            } while (ok && peek(word) < need);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                  // no instruction: keeps the record accesses behind the poll
+        return ok;
+    }
+    __device__ __forceinline__ void fail(int bh) const { __hip_atomic_store(err, 1u + (unsigned)bh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+};
+__global__ __launch_bounds__(NT16) void mlp_pair16_kernel(wv::Mlp16ChunkParams c, Pair16Params q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    const int b = (int)blockIdx.x;
+    if (b < q.nbh) {
+        DeviceHandover ho(q, b);
+        mlp16::pair::state_role(bk, ho, c, b);
+    } else if (b >= q.nbh8) {
+        DeviceHandover ho(q, b - q.nbh8);
+        mlp16::pair::output_role(bk, ho, c, b - q.nbh8);
+    }
 }
 
 // TTT-MLP backward at mini-batches of 16 (ttt_mlp16_bwd_body.h): one workgroup of eight waves per (b, h), each owning a slice of 32 hidden
@@ -274,6 +331,35 @@ void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*
     const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
     const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
     hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, c);
+}
+
+// The pair form of the scan above (opt-in: ttt_hip_mlp_forward_chunk_pair16).  `ws`: scan_pair16_workspace_bytes(n_bh) bytes - the flag
+// words of every (b, h) first, in a block of their own that is zeroed in front of EVERY launch, then the rings.  Both workgroups of
+// every pair must be resident (role B polls): where n_bh8 + n_bh workgroups do not fit the device the one-workgroup kernel runs.
+// 0 = enqueued as pairs, 1 = enqueued on the one-workgroup kernel, -1 = no host-mapped error word (nothing enqueued).
+size_t scan_pair16_workspace_bytes(int n_bh) { return mlp16::pair::workspace_bytes(n_bh); }
+int launch_scan_forward_pair16(const ScanParams& p, int n_bh, void* ws, hipStream_t s) {
+    const int n_bh8 = (n_bh + 7) & ~7;
+    if (n_bh8 + n_bh > device_cu_count()) {
+        launch_scan_forward_cs16(p, n_bh, nullptr, s);
+        return 1;
+    }
+    unsigned* err = sweep_error_word();
+    if (!err) return -1;
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::mlp_pair16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::pair::PAIR_LDS);
+    });
+    const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
+    const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
+    v16::Pair16Params q = {};
+    q.flags = (unsigned*)ws;
+    q.ring = (char*)ws + mlp16::pair::flags_bytes(n_bh);
+    q.err = err;
+    q.nbh = n_bh; q.nbh8 = n_bh8;
+    (void)hipMemsetAsync(q.flags, 0, mlp16::pair::flags_bytes(n_bh), s);       // the flags restart at 0 for every launch
+    hipLaunchKernelGGL(v16::mlp_pair16_kernel, dim3(n_bh8 + n_bh), dim3(v16::NT16), mlp16::pair::PAIR_LDS, s, c, q);
+    return 0;
 }
 
 void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s) {

@@ -47,6 +47,10 @@ int device_cu_count();                // compute units of the current device (ca
 int get_debug_fast_records();
 // mini-batches of 16 tokens, forward only (ttt_mfma16.hip): the evaluation / sampling geometry
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long* dbg, hipStream_t s);
+// the same scan as a PAIR of workgroups per (b,h) (ttt_mlp16_pair_body.h, opt-in): 0 = pairs, 1 = the one-workgroup kernel (the pairs do
+// not fit the device), -1 = no error word; `ws`: scan_pair16_workspace_bytes(n_bh) bytes
+int launch_scan_forward_pair16(const ScanParams& p, int n_bh, void* ws, hipStream_t s);
+size_t scan_pair16_workspace_bytes(int n_bh);
 void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s);       // TTT-MLP backward, one 8-wave workgroup per (b,h)
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h); whole sequence or a part
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);

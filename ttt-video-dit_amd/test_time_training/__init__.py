@@ -161,6 +161,12 @@ _PROTOTYPES_BWD_PARTS = {
     "ttt_hip_linear_recompute_groups": _sig("2p 2i p z p"),
     "ttt_hip_linear_sweep_groups": _sig("2p 2i p z p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_pair16.h, the fourth header: the TTT-MLP forward scan at mini-batches of 16 as a
+# pair of workgroups per (b, h) (tests/test_abi_pair16_cpu.py compares the two)
+_PROTOTYPES_PAIR16 = {
+    "ttt_hip_mlp_forward_pair16_workspace": _sig("p", ctypes.c_size_t),
+    "ttt_hip_mlp_forward_chunk_pair16": _sig("2p 2i 5p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -182,7 +188,7 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(_LIB_PATH)
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -422,6 +428,43 @@ def ttt_forward_chunk(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_s
     # the workspace is ttt_forward's (the pair scan's ring of state records); the final state goes where the initial one came from
     _launch("ttt_hip_mlp_forward", dims, args, device, suffix="_chunk",
             extra=(int(step0), int(nsteps), args.W1_init, args.b1_init, args.W2_init, args.b2_init))
+
+
+def _launch_pair16(dims, args, device, step0, nsteps, finals) -> bool:
+    """``ttt_hip_mlp_forward_chunk_pair16`` (include/ttt_hip_pair16.h) with its workspace from the per-stream cache -> True when the
+    scan was enqueued as pairs, False when the library enqueued the one-workgroup kernel (the pairs do not fit the device)"""
+    lib = load_library()
+    ws_bytes = lib.ttt_hip_mlp_forward_pair16_workspace(ctypes.byref(dims))
+    stream = torch.cuda.current_stream(device).cuda_stream
+    ws = _workspace(device, stream, ws_bytes) if ws_bytes else None
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_mlp_forward_chunk_pair16(ctypes.byref(dims), ctypes.byref(args), int(step0), int(nsteps), *finals,
+                                                  _p(ws), ws_bytes, stream)
+    if rc not in (0, 1):
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    return rc == 0
+
+
+def ttt_forward_pair16(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
+                       W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch, checkpoint_group_size) -> bool:
+    """``ttt_forward`` at mini-batches of 16 (bf16, head dim 64, MFMA scan) as a PAIR of workgroups per (b, h) - one carries the state,
+    the other computes the outputs from the records the first publishes (csrc/ttt_mlp16_pair_body.h; opt-in) - with the bits of
+    ``ttt_forward``.  Returns True when pairs ran, False when the one-workgroup kernel ran instead (see ``_launch_pair16``)."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
+               W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_MlpFwd, _MLP_FWD_SPEC, tensors, checkpoint_group_size)
+    return _launch_pair16(dims, args, device, 0, dims.NC, (None, None, None, None))
+
+
+def ttt_forward_chunk_pair16(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W2_state, b2_state,
+                             W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch, checkpoint_group_size, step0,
+                             nsteps) -> bool:
+    """``ttt_forward_chunk`` at mini-batches of 16 in pair form (``ttt_forward_pair16``): steps [step0, step0 + nsteps), the fp32 state
+    in ``*_state`` REPLACED by the state after the last step.  Returns True when pairs ran."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W2_state, b2_state,
+               W1_checkpoints, b1_checkpoints, W2_checkpoints, b2_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_MlpFwd, _MLP_FWD_SPEC, tensors, checkpoint_group_size)
+    return _launch_pair16(dims, args, device, step0, nsteps, (args.W1_init, args.b1_init, args.W2_init, args.b2_init))
 
 
 def ttt_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,

@@ -158,6 +158,7 @@ class FusedPreScanMLP(torch.autograd.Function):
         last_eta = eta.to(_BF16)[:, :, :, -1, :, None].contiguous()
 
         def run():
+            from ttt_amd.models.ssm.mlp_tk import mlp_forward_call
             from ttt_amd.models.ssm.pipeline import injected
             pre = injected("scan")           # (a pipelined forward: the scan has walked the sequence part by part already)
             if pre is not None:
@@ -170,7 +171,7 @@ class FusedPreScanMLP(torch.autograd.Function):
             out = torch.empty(B, NH, NC, CS, Fh, device=q.device, dtype=_BF16)
             cks = (torch.empty(B, NH, K, Fh, 4 * Fh, device=q.device, dtype=_F32), torch.empty(B, NH, K, 1, 4 * Fh, device=q.device, dtype=_F32),
                    torch.empty(B, NH, K, 4 * Fh, Fh, device=q.device, dtype=_F32), torch.empty(B, NH, K, 1, Fh, device=q.device, dtype=_F32))
-            ext.ttt_forward(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, *state, *cks, out, G)
+            mlp_forward_call(ext, mb(XQ), G)(mb(XQ), mb(XK), mb(XV), last_eta, lw, lb, *state, *cks, out, G)
             return (out, *cks)
 
         # (inside a checkpointed region that keeps "scan" the recomputation gets the scan output and the state checkpoints back)

@@ -29,9 +29,39 @@ def _check_cs16_bwd_impl(value):
     return value
 
 
+def _check_cs16_scan_pair(value):
+    if isinstance(value, str) and value.strip() in ("0", "1"):
+        value = int(value)
+    if isinstance(value, bool) or value not in (0, 1):
+        raise ValueError(f"TTTBase.cs16_scan_pair / TTT_MLP_CS16_SCAN_PAIR: expected 0 or 1, got {value!r}")
+    return int(value)
+
+
 def _ext():
     import test_time_training  # the HIP extension (raises if its library is missing)
     return test_time_training
+
+
+def _scan_pair_applies(ext, XQ, G):
+    """``TTTBase.cs16_scan_pair`` is on and this forward is what the pair scan serves: bf16, head dim 64, mini-batches of 16, on the
+    MFMA scan.  Off (the default): nothing is asked of the extension."""
+    from ttt_amd.models.ssm.ttt_layer import TTTBase
+    if not _check_cs16_scan_pair(TTTBase.cs16_scan_pair):
+        return False
+    B, NH, NC, CS, F = XQ.shape
+    if CS != 16 or F != 64 or XQ.dtype != _BF16:
+        return False
+    return ext.resolved_impl(B, NH, NC, CS, F, int(G), _BF16, mlp=True, backward=False) == "mfma"
+
+
+def mlp_forward_call(ext, XQ, G):
+    """the binding's TTT-MLP forward for this call: ``ttt_forward`` unless the pair switch applies (same arguments, same bits)"""
+    return ext.ttt_forward_pair16 if _scan_pair_applies(ext, XQ, G) else ext.ttt_forward
+
+
+def mlp_forward_chunk_call(ext, XQ, G):
+    """... and its forward over a part of the sequence: ``ttt_forward_chunk`` unless the pair switch applies"""
+    return ext.ttt_forward_chunk_pair16 if _scan_pair_applies(ext, XQ, G) else ext.ttt_forward_chunk
 
 
 def _last_row(eta: torch.Tensor, act_dtype) -> torch.Tensor:
@@ -77,7 +107,7 @@ class TkMLP(torch.autograd.Function):
         out = torch.empty(B, NH, NC, CS, F, device=dev, dtype=act)
         cks = (torch.empty(B, NH, K, F, 4 * F, device=dev, dtype=_F32), torch.empty(B, NH, K, 1, 4 * F, device=dev, dtype=_F32),
                torch.empty(B, NH, K, 4 * F, F, device=dev, dtype=_F32), torch.empty(B, NH, K, 1, F, device=dev, dtype=_F32))
-        ext.ttt_forward(XQ, XK, XV, last_eta, ln_w, ln_b, *state, *cks, out, G)
+        mlp_forward_call(ext, XQ, G)(XQ, XK, XV, last_eta, ln_w, ln_b, *state, *cks, out, G)
 
         ctx.save_for_backward(XQ, XV, XK, last_eta, ln_w, ln_b, *cks)   # XQW is not an input of the backward arithmetic
         ctx.G = G

@@ -183,8 +183,14 @@ class ScanKind:
         self.result, self.ck_shapes, self.ln_shape, self.chunk = result, ck_shapes, ln_shape, chunk
 
 
-MLP_SCAN = ScanKind("scan", lambda F: ((F, 4 * F), (1, 4 * F), (4 * F, F), (1, F)), lambda NH, F: (1, NH, 1, F),
-                    lambda ext, impl: ext.ttt_forward_chunk)
+def _mlp_chunk(ext, impl):
+    """``ext.ttt_forward_chunk``, or - ``TTTBase.cs16_scan_pair`` on, at mini-batches of 16 on the MFMA scan - its pair form; picked per
+    call from XQ's shape and the checkpoint group size (arguments: ..., out, G, step0, nsteps)"""
+    from ttt_amd.models.ssm.mlp_tk import mlp_forward_chunk_call
+    return lambda XQ, *a: mlp_forward_chunk_call(ext, XQ, a[-3])(XQ, *a)
+
+
+MLP_SCAN = ScanKind("scan", lambda F: ((F, 4 * F), (1, 4 * F), (4 * F, F), (1, F)), lambda NH, F: (1, NH, 1, F), _mlp_chunk)
 LINEAR_SCAN = ScanKind("scan_lin", lambda F: ((F, F), (1, F)), lambda NH, F: (NH, F),
                        lambda ext, impl: (lambda *a: ext.ttt_linear_forward_chunk(impl, *a)))
 

@@ -28,7 +28,7 @@ from ttt_amd.models.cogvideo.utils import SequenceMetadata
 from ttt_amd.models.configs import ModelConfig
 from ttt_amd.models.ssm.fused import FusedPost, FusedPre, FusedPreScanMLP, fused_available
 from ttt_amd.models.ssm.linear_hip import HipLinear, TritonLinear  # noqa: F401
-from ttt_amd.models.ssm.mlp_tk import TkMLP
+from ttt_amd.models.ssm.mlp_tk import TkMLP, _check_cs16_scan_pair
 from ttt_amd.models.ssm.ops import ttt_linear, ttt_mlp
 from ttt_amd.models.ssm.utils import apply_rotary_emb, precompute_freqs_cis_3d
 
@@ -118,6 +118,13 @@ def reversal_map(meta: SequenceMetadata, seq_len: int) -> torch.Tensor:
 
 
 class TTTBase(nn.Module):
+    # The TTT-MLP forward scan at mini-batches of 16 (bf16, head dim 64, MFMA scan) as a PAIR of workgroups per (b, h) - one carries the
+    # state, the other computes the outputs (csrc/ttt_mlp16_pair_body.h): 0 (default) = the one-workgroup kernel, 1 = the pair entries
+    # of the binding (ttt_forward_pair16 / ttt_forward_chunk_pair16), in one piece and in the parts of pipeline.py, with grad enabled or
+    # not (role A writes the checkpoints); the same bits either way.  A class attribute, read at every call (like TkMLP.cs16_bwd_impl);
+    # ignored at every other geometry.  Environment variable TTT_MLP_CS16_SCAN_PAIR.
+    cs16_scan_pair = _check_cs16_scan_pair(os.environ.get("TTT_MLP_CS16_SCAN_PAIR", "0"))
+
     def __init__(self, config: ModelConfig):
         super().__init__()
         self.config = config

@@ -6,6 +6,7 @@
 #include "../../include/ttt_hip_parts.h"
 #include "../../include/ttt_hip_bwd_parts.h"
 #include "../../include/ttt_hip_pair16.h"
+#include "../../include/ttt_hip_mlp_bwd_parts.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -327,6 +328,54 @@ int ttt_hip_linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a,
         return fail("ttt_hip: linear_sweep_groups: ln_carry null or smaller than ttt_hip_linear_backward_parts_carry(d)");
     ttt::mfma::linear_sweep_groups(d, a, k0, nk, slots, ln_carry, (hipStream_t)stream);
     return post_launch("linear_sweep_groups");
+}
+
+// include/ttt_hip_mlp_bwd_parts.h
+// The parts exist on the MFMA body alone, so TTT_IMPL_AUTO has nothing to choose between here and takes it (as the linear entries take
+// AUTO where AUTO means their MFMA sweep); what ttt_hip_mlp_backward resolves AUTO to is not touched.  TTT_IMPL_GENERIC is refused.
+static bool mlp_bwd_parts_serves(const ttt_dims* d) {
+    return d->act_dtype == TTT_DTYPE_BF16 && d->F == 64 && d->CS == 16 && d->impl != TTT_IMPL_GENERIC;
+}
+static int check_mlp_bwd_parts(const char* fmt_what, const ttt_dims* d, int k0, int nk, const void* slots, size_t slots_bytes) {
+    if (!mlp_bwd_parts_serves(d))
+        return fail("ttt_hip: %s: only the MFMA backward at mini-batches of 16 (bf16 activations, F = 64, TTT_IMPL_MFMA or TTT_IMPL_AUTO) runs over a range of checkpoint groups", fmt_what);
+    const int K = (d->NC + d->G - 1) / d->G;
+    if (k0 < 0 || nk <= 0 || k0 > K - nk) return fail("ttt_hip: %s: the groups [k0, k0 + nk) must lie inside [0, K)", fmt_what);
+    if (!slots || slots_bytes < ttt::mfma::mlp_backward_parts_slots(d, nk))
+        return fail("ttt_hip: %s: slot workspace null or smaller than ttt_hip_mlp_backward_parts_slots(d, nk)", fmt_what);
+    if ((uintptr_t)slots & 15) return fail("ttt_hip: %s: the slot workspace must be 16-byte aligned", fmt_what);
+    return 0;
+}
+size_t ttt_hip_mlp_backward_parts_slots(const ttt_dims* d, int nk) {
+    if (check_dims(d) || nk <= 0) return 0;
+    return ttt::mfma::mlp_backward_parts_slots(d, nk);
+}
+size_t ttt_hip_mlp_backward_parts_carry(const ttt_dims* d) {
+    if (check_dims(d)) return 0;
+    return ttt::mfma::mlp_backward_parts_carry(d);
+}
+int ttt_hip_mlp_recompute_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, void* slots, size_t slots_bytes, void* stream) {
+    if (check_dims(d)) return -1;
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints);
+    if (check_mlp_bwd_parts("mlp_recompute_groups", d, k0, nk, slots, slots_bytes)) return -1;
+    ttt::mfma::mlp_recompute_groups(d, a, k0, nk, slots, (hipStream_t)stream);
+    return post_launch("mlp_recompute_groups");
+}
+int ttt_hip_mlp_sweep_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
+                             float* ln_carry, size_t carry_bytes, void* stream) {
+    if (check_dims(d)) return -1;
+    if (!a) return fail("ttt_hip: null args");
+    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_W2_last); NEED(grad_L_b2_last); NEED(grad_L_XQW);
+    NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias); NEED(grad_L_W1_init); NEED(grad_L_b1_init);
+    NEED(grad_L_W2_init); NEED(grad_L_b2_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
+    if (check_mlp_bwd_parts("mlp_sweep_groups", d, k0, nk, slots, slots_bytes)) return -1;
+    if (!ln_carry || carry_bytes < ttt::mfma::mlp_backward_parts_carry(d) || ((uintptr_t)ln_carry & 15))
+        return fail("ttt_hip: mlp_sweep_groups: ln_carry null, not 16-byte aligned or smaller than ttt_hip_mlp_backward_parts_carry(d)");
+    ttt::mfma::mlp_sweep_groups(d, a, k0, nk, slots, ln_carry, (hipStream_t)stream);
+    return post_launch("mlp_sweep_groups");
 }
 
 /* ---- fused pre / post-processing of the TTT layer (ttt_prepost.hip) --------------------------------- */

@@ -38,7 +38,7 @@ void mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, hipStre
     else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
 }
 // TTT-MLP backward at CS = 16: the per-step state lives in the caller's four *_init_group buffers, nothing in `ws`
-void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t s) {
+static wv::Mlp16BwdParams mlp16_bwd_params(const ttt_dims* d, const ttt_mlp_bwd_args* a) {
     wv::Mlp16BwdParams p = {};
     p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
     p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
@@ -50,7 +50,24 @@ void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t
     p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init; p.dW2 = a->grad_L_W2_init; p.db2 = a->grad_L_b2_init;
     p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
     p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    launch_mlp_backward_cs16(p, d->B * d->NH, s);
+    return p;
+}
+void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t s) {
+    launch_mlp_backward_cs16(mlp16_bwd_params(d, a), d->B * d->NH, s);
+}
+// The same backward in parts (ttt_wave_types.h: Mlp16BwdPartParams).  G slots per group: the fp32 state entering each step ; the
+// carry: the 2 x 16 x 64 cells of the owners' dln shares per (b, h).
+size_t mlp_backward_parts_slots(const ttt_dims* d, int nk) {
+    return (size_t)d->B * d->NH * (size_t)nk * (size_t)d->G * wv::MLP16_PART_SLOT_BYTES;
+}
+size_t mlp_backward_parts_carry(const ttt_dims* d) { return (size_t)d->B * d->NH * wv::MLP16_PART_CARRY_FLOATS * sizeof(float); }
+void mlp_recompute_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, void* slots, hipStream_t s) {
+    const wv::Mlp16BwdPartParams q = {mlp16_bwd_params(d, a), k0, nk, (float*)slots, nullptr};
+    launch_mlp_recompute_groups(q, d->B * d->NH, s);
+}
+void mlp_sweep_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, const void* slots, float* ln_carry, hipStream_t s) {
+    const wv::Mlp16BwdPartParams q = {mlp16_bwd_params(d, a), k0, nk, (float*)const_cast<void*>(slots), ln_carry};
+    launch_mlp_sweep_groups(q, d->B * d->NH, s);
 }
 // steps [step0, step0 + nsteps) of the scan: the same kernel over a part of the sequence, started from the state in
 // a->*_init (what the previous part left in *_final), its checkpoints written at their places in the whole sequence's arrays.

@@ -220,6 +220,20 @@ __global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_bwd16_kernel(wv::M
     mlp16::bwd::backward(bk, p, blockIdx.x);
 }
 
+// The same backward in parts (mlp16::bwd::recompute_groups / sweep_groups): the recompute of a range of checkpoint groups, one workgroup
+// per (b, h, group) - any number of them, none waits for another - into the caller's slot workspace, and the reverse walk over the range
+// from those slots, one workgroup per (b, h).  Same LDS map as the one-call kernel.
+__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_recompute16_groups_kernel(wv::Mlp16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    mlp16::bwd::recompute_groups(bk, q, blockIdx.x);
+}
+__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_sweep16_groups_kernel(wv::Mlp16BwdPartParams q) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    mlp16::bwd::sweep_groups(bk, q, blockIdx.x);
+}
+
 // backward: one wave per workgroup (48 .. 96 scans on 256 CUs: a CU of its own per scan; up to 512 registers per lane)
 __global__ __launch_bounds__(64) void linear_bwd16_kernel(wv::Lin16Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -368,6 +382,22 @@ void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t
         (void)hipFuncSetAttribute((const void*)v16::mlp_bwd16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
     });
     hipLaunchKernelGGL(v16::mlp_bwd16_kernel, dim3(n_bh), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, p);
+}
+
+static void mlp_parts_attr_once() {
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::mlp_recompute16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
+        (void)hipFuncSetAttribute((const void*)v16::mlp_sweep16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
+    });
+}
+void launch_mlp_recompute_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s) {
+    mlp_parts_attr_once();
+    hipLaunchKernelGGL(v16::mlp_recompute16_groups_kernel, dim3(n_bh * q.nk), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, q);
+}
+void launch_mlp_sweep_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s) {
+    mlp_parts_attr_once();
+    hipLaunchKernelGGL(v16::mlp_sweep16_groups_kernel, dim3(n_bh), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, q);
 }
 
 }  // namespace mfma

@@ -52,6 +52,9 @@ void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*
 int launch_scan_forward_pair16(const ScanParams& p, int n_bh, void* ws, hipStream_t s);
 size_t scan_pair16_workspace_bytes(int n_bh);
 void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s);       // TTT-MLP backward, one 8-wave workgroup per (b,h)
+// the same backward in parts: recompute grid n_bh * q.nk, sweep grid n_bh, eight waves each
+void launch_mlp_recompute_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s);
+void launch_mlp_sweep_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s);
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h); whole sequence or a part
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h); whole sequence or a part

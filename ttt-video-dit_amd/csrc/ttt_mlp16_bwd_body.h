@@ -153,9 +153,23 @@ TTT_WV_FN f32x4 gather(BK& bk, int red_off, int ot, int of0, f32x4 z) {
     return z;
 }
 
-// the state entering steps lo .. lo + n - 1 of group k -> slots 0 .. n - 1 of the *_init_group buffers
-template <class BK>
-TTT_WV_FN void recompute_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n) {
+// Where the per-step state of a group lives: slot j of the group is element first + j of four arrays.  One call: the caller's four
+// *_init_group buffers, G slots per (b, h), each array dense (PACKED = false).  In parts: the slot workspace [B*NH][nk][G] of
+// MLP16_PART_SLOT_FLOATS, the four arrays interleaved slot by slot (PACKED = true).  The strides are compile-time either way.
+struct SlotView {
+    float *W1, *b1, *W2, *b2;
+    size_t first;
+};
+template <bool PACKED>
+struct SlotStride {
+    static constexpr size_t W1 = PACKED ? MLP16_PART_SLOT_FLOATS : 64 * 256, b1 = PACKED ? MLP16_PART_SLOT_FLOATS : 256,
+                            W2 = PACKED ? MLP16_PART_SLOT_FLOATS : 256 * 64, b2 = PACKED ? MLP16_PART_SLOT_FLOATS : 64;
+};
+
+// the state entering steps lo .. lo + n - 1 of group k -> slots 0 .. n - 1 of the group (sv)
+template <bool PACKED, class BK>
+TTT_WV_FN void recompute_group(BK& bk, const Mlp16BwdParams& p, const SlotView& sv, int bh, int k, int n) {
+    typedef SlotStride<PACKED> SS;
     const int tid0 = bk.thread(), wv = bk.wave(), l0 = bk.lane();
     const size_t ck = (size_t)bh * p.K + k;
 
@@ -199,7 +213,7 @@ TTT_WV_FN void recompute_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, i
         for (int fb = 0; fb < 4; ++fb) W2F[s][fb] = stack(W2t[s][0][fb], W2t[s][1][fb]);
     }
 
-    const size_t tile0 = (size_t)bh * p.NC + (size_t)k * p.G, slot0 = (size_t)bh * p.G;
+    const size_t tile0 = (size_t)bh * p.NC + (size_t)k * p.G, slot0 = sv.first;
 
     for (int j = 0; j < n; ++j) {
         int l = bk.opaque(l0), g = l >> 4, i = l & 15;
@@ -211,7 +225,7 @@ TTT_WV_FN void recompute_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, i
         const size_t sl = slot0 + j;
 #pragma unroll
         for (int s = 0; s < NS; ++s)
-            store_state(p.W1s + sl * 64 * 256, p.b1s + sl * 256, p.W2s + sl * 256 * 64, p.b2s + sl * 64, W1t[s], W2Tt[s], b1v[s], b2v,
+            store_state(sv.W1 + sl * SS::W1, sv.b1 + sl * SS::b1, sv.W2 + sl * SS::W2, sv.b2 + sl * SS::b2, W1t[s], W2Tt[s], b1v[s], b2v,
                         NS * wv + s, g, i);
         if (j == n - 1) break;
         const size_t tile = tile0 + j;
@@ -329,12 +343,13 @@ TTT_WV_FN void recompute_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, i
     bk.barrier();      // the slots are complete (each wave re-reads its own slices) and the LDS is free for the reverse walk
 }
 
-// the reverse walk over the n steps of group k from the slots; an owner thread's share of dln_w / dln_b accumulates in its cell of
-// B_DLNW / B_DLNB (eight registers less across the whole walk)
-template <class BK>
-TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n) {
+// the reverse walk over the n steps of group k from the slots (sv); an owner thread's share of dln_w / dln_b accumulates in its cell of
+// B_DLNW / B_DLNB (eight registers less across the whole walk).  `last`: the state gradient comes from the upstream p.d*_last (the
+// first group a call walks) and not from where the previous group parked it (p.dW1 .. p.db2, where this group parks it in turn).
+template <bool PACKED, class BK>
+TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, const SlotView& sv, int bh, int k, int n, bool last) {
+    typedef SlotStride<PACKED> SS;
     const int tid0 = bk.thread(), wv = bk.wave(), l0 = bk.lane();
-    const bool last = k == p.K - 1;
     const bf16x4 ONES = {(__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f};
 
     f32x4 dW1t[NS][4][2], dW2Tt[NS][4][2];          // (rows = f, lane = n)
@@ -354,7 +369,7 @@ TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n
     }
 
     // staging: chunks of 16 bytes, 128 per tile, in the order K, V, Q, dOut
-    const size_t tile0 = (size_t)bh * p.NC + (size_t)k * p.G, slot0 = (size_t)bh * p.G;
+    const size_t tile0 = (size_t)bh * p.NC + (size_t)k * p.G, slot0 = sv.first;
 
     for (int j = n - 1; j >= 0; --j) {
         int l = bk.opaque(l0), g = l >> 4, i = l & 15;
@@ -362,8 +377,8 @@ TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n
         const int lt0 = tid & 127, lofs = ((lt0 >> 3) * TS + (lt0 & 7) * 8) * 2;      // staging: this thread's 16-byte chunk of a tile
         const size_t gofs = (size_t)(lt0 >> 3) * 64 + (lt0 & 7) * 8;
         const size_t tile = tile0 + j, sl = slot0 + j;
-        const float* W1s = p.W1s + sl * 64 * 256;
-        const float* W2s = p.W2s + sl * 256 * 64;
+        const float* W1s = sv.W1 + sl * SS::W1;
+        const float* W2s = sv.W2 + sl * SS::W2;
 
 #pragma unroll
         for (int c = 0; c < 512; c += 64 * WAVES) {
@@ -372,7 +387,7 @@ TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n
             bk.template lds_store<u32x4>((w == 0 ? B_K : w == 1 ? B_V : w == 2 ? B_Q : B_D) + lofs, *reinterpret_cast<const u32x4*>(src + tile * 1024 + gofs));
         }
         if (tid < 16) bk.template lds_store<float>(B_ETA + tid * 4, (float)p.eta[tile * 16 + tid]);
-        if (tid < 64) bk.template lds_store<float>(B_B2 + tid * 4, p.b2s[sl * 64 + tid]);
+        if (tid < 64) bk.template lds_store<float>(B_B2 + tid * 4, sv.b2[sl * SS::b2 + tid]);
         bk.barrier();                                                                                   // S0
         TTT_MLP16_BLOCK_END();
 
@@ -386,7 +401,7 @@ TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n
             for (int s = 0; s < NS; ++s) {
                 const int vw = NS * wv + s, n0 = 32 * vw, img = B_XIMG + vw * XIMG_BYTES, wimg = B_WIMG + vw * WIMG_BYTES;
 #pragma unroll
-                for (int nb = 0; nb < 2; ++nb) b1n[s][nb] = p.b1s[sl * 256 + n0 + 16 * nb + i];
+                for (int nb = 0; nb < 2; ++nb) b1n[s][nb] = sv.b1[sl * SS::b1 + n0 + 16 * nb + i];
                 bf16x8 W1B[2][2];
                 {
                     f32x4 W1t[4][2];
@@ -469,7 +484,7 @@ TTT_WV_FN void sweep_group(BK& bk, const Mlp16BwdParams& p, int bh, int k, int n
             const bf16x8 gA0 = rho_readx(bk, g, i, B_G, 0), gA1 = rho_readx(bk, g, i, B_G, 32);
             const bf16x8 zA0 = rho_readx(bk, g, i, B_GZ, 0), zA1 = rho_readx(bk, g, i, B_GZ, 32);
 #pragma unroll
-            for (int fb = 0; fb < 4; ++fb) b2n[fb] = p.b2s[sl * 64 + 16 * fb + i] + bk.mma16(ONES, tr4x(bk, g, i, B_G, TS, 0, 16 * fb), zero4())[0];
+            for (int fb = 0; fb < 4; ++fb) b2n[fb] = sv.b2[sl * SS::b2 + 16 * fb + i] + bk.mma16(ONES, tr4x(bk, g, i, B_G, TS, 0, 16 * fb), zero4())[0];
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int vw = NS * wv + s, n0 = 32 * vw, img = B_XIMG + vw * XIMG_BYTES, wimg = B_WIMG + vw * WIMG_BYTES;
@@ -870,11 +885,71 @@ TTT_WV_FN void backward(BK& bk, const Mlp16BwdParams& p, int bh) {
     }
     for (int k = p.K - 1; k >= 0; --k) {
         const int n = (k + 1) * p.G <= p.NC ? p.G : p.NC - k * p.G;
-        recompute_group(bk, p, bh, k, n);
-        sweep_group(bk, p, bh, k, n);
+        const SlotView sv = {p.W1s, p.b1s, p.W2s, p.b2s, (size_t)bh * p.G};      // the caller's four *_init_group buffers
+        recompute_group<false>(bk, p, sv, bh, k, n);
+        sweep_group<false>(bk, p, sv, bh, k, n, k == p.K - 1);
     }
     // dln_w, dln_b: the owners' shares summed over the 16 tokens in token order (the last walk ended with a barrier)
     if (tid < 128) {
+        const int f = tid & 63, red = tid < 64 ? B_DLNW : B_DLNB;
+        float sm = 0.f;
+        for (int ot = 0; ot < 16; ++ot) sm += bk.template lds_load<float>(red + (ot * 64 + f) * 4);
+        (tid < 64 ? p.dln_w : p.dln_b)[(size_t)bh * 64 + f] = sm;
+    }
+}
+
+// ---- The backward in parts (Mlp16BwdPartParams, ttt_wave_types.h): the two halves of backward() above as kernels of their own over
+// the checkpoint groups [k0, k0 + nk).  The recompute of a group depends on its checkpoint alone, the walk on the state gradient the
+// later groups leave; both run recompute_group / sweep_group above, so every step is a step of backward(), rounded alike, and a slot
+// holds the bits backward() leaves in the *_init_group buffers.  Within recompute_groups no workgroup reads a slot another wrote,
+// within sweep_groups no wave writes one.
+TTT_WV_FN SlotView part_slots(const Mlp16BwdPartParams& q, int bh, int k) {
+    float* s = q.slots;
+    return {s + MLP16_PART_W1_OFS, s + MLP16_PART_B1_OFS, s + MLP16_PART_W2_OFS, s + MLP16_PART_B2_OFS,
+            ((size_t)bh * q.nk + (size_t)(k - q.k0)) * q.p.G};
+}
+// unit of work bhk = bh * nk + (k - k0): group k of (b, h) = bh
+template <class BK>
+TTT_WV_FN void recompute_groups(BK& bk, const Mlp16BwdPartParams& q, int bhk) {
+    const Mlp16BwdParams& p = q.p;
+    const int tid = bk.thread(), bh = bhk / q.nk, k = q.k0 + bhk % q.nk, head = bh % p.NH;
+    if (tid < 64) {
+        bk.template lds_store<float>(B_GAM + tid * 4, p.ln_w[(size_t)head * 64 + tid]);
+        bk.template lds_store<float>(B_BET + tid * 4, p.ln_b[(size_t)head * 64 + tid]);
+    }
+    const int n = (k + 1) * p.G <= p.NC ? p.G : p.NC - k * p.G;
+    recompute_group<true>(bk, p, part_slots(q, bh, k), bh, k, n);
+}
+// the reverse walk of (b, h) = bh over the groups k0 + nk - 1 .. k0 from the slots recompute_groups left.  Carries dW1 .. db2 (from
+// p.d*_last into p.dW1 .. p.db2, which may be the same buffers: every thread has read its cells before any thread writes, S0 .. S8
+// lie between) and the owners' dln shares: the B_DLNW / B_DLNB cells start from zero where the range ends the sequence and from
+// q.ln_carry otherwise, go back there at the end, and the range that holds group 0 reduces them as backward() does.
+template <class BK>
+TTT_WV_FN void sweep_groups(BK& bk, const Mlp16BwdPartParams& q, int bh) {
+    const Mlp16BwdParams& p = q.p;
+    const int tid = bk.thread(), head = bh % p.NH;
+    float* carry = q.ln_carry + (size_t)bh * MLP16_PART_CARRY_FLOATS;
+    if (tid < 64) {
+        bk.template lds_store<float>(B_GAM + tid * 4, p.ln_w[(size_t)head * 64 + tid]);
+        bk.template lds_store<float>(B_BET + tid * 4, p.ln_b[(size_t)head * 64 + tid]);
+    }
+    if (tid < 256) {
+        const int ot = tid >> 4, of0 = 4 * (tid & 15);
+        const bool fresh = q.k0 + q.nk == p.K;
+        bk.template lds_store<f32x4>(B_DLNW + (ot * 64 + of0) * 4, fresh ? zero4() : *reinterpret_cast<const f32x4*>(carry + ot * 64 + of0));
+        bk.template lds_store<f32x4>(B_DLNB + (ot * 64 + of0) * 4, fresh ? zero4() : *reinterpret_cast<const f32x4*>(carry + 1024 + ot * 64 + of0));
+    }
+    // (no barrier: a cell of B_DLNW / B_DLNB is its owner's alone during the walk, and S0 lies in front of the first read of B_GAM / B_BET)
+    for (int k = q.k0 + q.nk - 1; k >= q.k0; --k) {
+        const int n = (k + 1) * p.G <= p.NC ? p.G : p.NC - k * p.G;
+        sweep_group<true>(bk, p, part_slots(q, bh, k), bh, k, n, k == q.k0 + q.nk - 1);
+    }
+    if (tid < 256) {      // an owner's own cells (the last walk ended with a barrier)
+        const int ot = tid >> 4, of0 = 4 * (tid & 15);
+        *reinterpret_cast<f32x4*>(carry + ot * 64 + of0) = bk.template lds_load<f32x4>(B_DLNW + (ot * 64 + of0) * 4);
+        *reinterpret_cast<f32x4*>(carry + 1024 + ot * 64 + of0) = bk.template lds_load<f32x4>(B_DLNB + (ot * 64 + of0) * 4);
+    }
+    if (q.k0 == 0 && tid < 128) {
         const int f = tid & 63, red = tid < 64 ? B_DLNW : B_DLNB;
         float sm = 0.f;
         for (int ot = 0; ot < 16; ++ot) sm += bk.template lds_load<float>(red + (ot * 64 + f) * 4);

@@ -96,5 +96,22 @@ struct Mlp16BwdParams {
     float eps;
 };
 
+// the TTT-MLP backward at mini-batches of 16 in parts (ttt_mlp16_bwd_body.h: recompute_groups, sweep_groups): the checkpoint groups
+// [k0, k0 + nk) of the K = p.K groups of the sequence that `p` describes (whole-sequence pointers; p.W1s .. p.b2s unused).
+// `slots`: [B*NH][nk][G] slots of MLP16_PART_SLOT_FLOATS fp32 - slot j of a group is the state ENTERING its step j: W1 [64,256],
+// b1 [256], W2 [256,64], b2 [64], one after the other (a ragged last group uses fewer than G).  recompute_groups writes them from the
+// checkpoints, sweep_groups reads them.  `ln_carry`: [B*NH][2][16][64] fp32, the owner threads' un-reduced shares of dln_w and dln_b
+// (the B_DLNW / B_DLNB cells of the one-call kernel's LDS), handed from one sweep_groups call to the next.
+constexpr size_t MLP16_PART_W1_OFS = 0, MLP16_PART_B1_OFS = 64 * 256, MLP16_PART_W2_OFS = MLP16_PART_B1_OFS + 256,
+                 MLP16_PART_B2_OFS = MLP16_PART_W2_OFS + 256 * 64, MLP16_PART_SLOT_FLOATS = MLP16_PART_B2_OFS + 64;
+constexpr size_t MLP16_PART_SLOT_BYTES = MLP16_PART_SLOT_FLOATS * sizeof(float);      // 132 352
+constexpr size_t MLP16_PART_CARRY_FLOATS = 2 * 16 * 64;
+struct Mlp16BwdPartParams {
+    Mlp16BwdParams p;
+    int k0, nk;
+    float* slots;
+    float* ln_carry;
+};
+
 }  // namespace wv
 }  // namespace ttt

@@ -167,6 +167,14 @@ _PROTOTYPES_PAIR16 = {
     "ttt_hip_mlp_forward_pair16_workspace": _sig("p", ctypes.c_size_t),
     "ttt_hip_mlp_forward_chunk_pair16": _sig("2p 2i 5p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_mlp_bwd_parts.h, the fifth header: the TTT-MLP backward at mini-batches of 16 over
+# ranges of checkpoint groups (tests/test_abi_mlp_bwd_parts_cpu.py compares the two)
+_PROTOTYPES_MLP_BWD_PARTS = {
+    "ttt_hip_mlp_backward_parts_slots": _sig("p i", ctypes.c_size_t),
+    "ttt_hip_mlp_backward_parts_carry": _sig("p", ctypes.c_size_t),
+    "ttt_hip_mlp_recompute_groups": _sig("2p 2i p z p"),
+    "ttt_hip_mlp_sweep_groups": _sig("2p 2i p z p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -188,7 +196,8 @@ def load_library() -> ctypes.CDLL:
     lib = ctypes.CDLL(_LIB_PATH)
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16,
+                                      **_PROTOTYPES_MLP_BWD_PARTS}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -640,6 +649,104 @@ def ttt_linear_sweep_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_nor
     if rc != 0:
         raise RuntimeError(lib.ttt_hip_last_error().decode())
     linear_bwd_parts_calls["sweep"] += 1
+
+
+# The TTT-MLP backward at mini-batches of 16 over ranges of checkpoint groups (include/ttt_hip_mlp_bwd_parts.h).  The recompute reads
+# XK, XV, last_eta, the LayerNorm parameters and the four checkpoint tensors; the sweep reads and writes everything else of
+# ``ttt_backward``'s list except the sixteen re-materialisation buffers.  What a call does not touch may be None; what is given is
+# checked against the contract of ``ttt_backward``, field by field.
+_MLP_RECOMPUTE_FIELDS = frozenset(("XK", "XV", "last_eta", "ttt_norm_weight", "ttt_norm_bias", "W1_checkpoints", "b1_checkpoints",
+                                   "W2_checkpoints", "b2_checkpoints"))
+_MLP_SWEEP_UNUSED = frozenset(("W1_checkpoints", "b1_checkpoints", "W2_checkpoints", "b2_checkpoints", "XQW")) | _MLP_BWD_SCRATCH
+mlp_bwd_parts_calls = {"recompute": 0, "sweep": 0}      # launches of this process (tests, tools)
+
+
+def _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, optional):
+    XQ = tensors[0] if tensors[0] is not None else tensors[1]          # (the recompute does not need XQ: XK has its shape)
+    _check5(XQ)
+    B, NH, NC, CS, F = XQ.shape
+    G = int(checkpoint_group_size)
+    sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
+    args = _fill_args(_MlpBwd, _MLP_BWD_SPEC, tensors, sizes, XQ.dtype, optional)
+    return _dims(B, NH, NC, CS, F, G, XQ.dtype, impl), args, XQ.device
+
+
+def mlp_backward_parts_slots(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of the slot workspace of ``ttt_recompute_groups`` / ``ttt_sweep_groups`` for ``nk`` checkpoint groups: B * NH * nk * G
+    slots of 132352 bytes (the fp32 W1, b1, W2, b2 entering a step)"""
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(load_library().ttt_hip_mlp_backward_parts_slots(ctypes.byref(d), int(nk)))
+
+
+def mlp_backward_parts_carry(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of ``ln_carry``: B * NH * 2 * 16 * 64 * 4"""
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(load_library().ttt_hip_mlp_backward_parts_carry(ctypes.byref(d)))
+
+
+def ttt_recompute_groups(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+                         b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+                         std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+                         x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+                         grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+                         grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+                         grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, *, impl=None):
+    """Re-run the state updates of the checkpoint groups [k0, k0 + nk) of the sequence the (whole-sequence) tensors describe from their
+    checkpoints and leave the fp32 state entering every step in ``slots`` (``mlp_backward_parts_slots`` bytes for nk groups) -
+    ``ttt_hip_mlp_recompute_groups``, include/ttt_hip_mlp_bwd_parts.h.  The tensor list of ``ttt_backward``; only XK, XV, last_eta, the
+    LayerNorm parameters and the four checkpoint tensors are needed, the rest may be None.  bf16, head dim 64, mini-batches of 16;
+    ``impl`` None (the global selector), 'auto' or 'mfma' - the parts exist on the MFMA body alone, 'generic' is refused."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+               b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+               std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+               x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+               grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+               grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+               grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(MLP_BWD_FIELDS) - _MLP_RECOMPUTE_FIELDS)
+    lib = load_library()
+    _device_bytes(slots, "slots")                 # (its size is the library's check: it knows whether the range is one)
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_mlp_recompute_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                              slots.numel() * slots.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    mlp_bwd_parts_calls["recompute"] += 1
+
+
+def ttt_sweep_groups(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+                     b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+                     std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+                     x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+                     grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+                     grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+                     grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, ln_carry, *, impl=None):
+    """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` ``ttt_recompute_groups`` left for the same range
+    (``ttt_hip_mlp_sweep_groups``).  Carries dW1 / db1 / dW2 / db2 from ``grad_L_*_last`` to ``grad_L_*_init`` (which may be the same
+    tensors) and the LayerNorm gradients' un-reduced shares in ``ln_carry`` (``mlp_backward_parts_carry`` bytes, fp32); the range with
+    k0 == 0 also writes ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from the last range to the first, the results are the bits of
+    ``ttt_backward_impl('mfma', ...)``.  The checkpoints, XQW_batch and the sixteen ``*_group`` buffers may be None.  The caller orders a
+    recompute before the sweep of its slots (same stream, or events)."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
+               b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
+               std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
+               x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
+               grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
+               grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
+               grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, _MLP_SWEEP_UNUSED)
+    lib = load_library()
+    _device_bytes(slots, "slots")
+    _device_bytes(ln_carry, "ln_carry")
+    if ln_carry.dtype != torch.float32:
+        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_mlp_sweep_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                          slots.numel() * slots.element_size(), _p(ln_carry),
+                                          ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    mlp_bwd_parts_calls["sweep"] += 1
 
 
 # ------------------------------------------------------------------------------------------------

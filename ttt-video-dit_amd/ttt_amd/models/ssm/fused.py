@@ -206,7 +206,9 @@ class FusedPreScanMLP(torch.autograd.Function):
         from ttt_amd.models.ssm.mlp_tk import TkMLP
         impl = TkMLP.bwd_impl(CS, Fh, _BF16)
         resolved = ext.resolved_impl(B, NH, NC, CS, Fh, G, _BF16, mlp=True, backward=True, impl=impl)
-        if resolved == "generic" or (resolved == "mfma" and CS == 16):
+        if TkMLP.bwd_parts(impl):      # (... unless it runs in parts - TkMLP.cs16_backward_parts -, from workspaces of its own)
+            remat = (None,) * 16
+        elif resolved == "generic" or (resolved == "mfma" and CS == 16):
             remat = (e32(B, NH, G, Fh, H), e32(B, NH, G, 1, H), e32(B, NH, G, H, Fh), e32(B, NH, G, 1, Fh)) + (None,) * 12
         else:
             remat = (None,) * 16

@@ -37,9 +37,64 @@ def _check_cs16_scan_pair(value):
     return int(value)
 
 
+def _cs16_backward_parts_default():
+    v = os.environ.get("TTT_MLP_CS16_BACKWARD_PARTS", "0")
+    if not v.isdigit():
+        raise ValueError(f"TTT_MLP_CS16_BACKWARD_PARTS: expected a non-negative integer (checkpoint groups per part, 0 = off), got {v!r}")
+    return int(v)
+
+
 def _ext():
     import test_time_training  # the HIP extension (raises if its library is missing)
     return test_time_training
+
+
+def part_ranges(K, gpp):
+    """(k0, nk) of the K checkpoint groups cut into ranges of ``gpp``, the LAST range first; the first range takes the remainder"""
+    return [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]
+
+
+def backward_in_parts(ext, gpp, tensors, G):
+    """``ttt_backward_impl("mfma", ...)`` at mini-batches of 16 as ranges of ``gpp`` checkpoint groups, walked from the last range to
+    the first (the entries of include/ttt_hip_mlp_bwd_parts.h), on the schedule of ``linear_hip.backward_in_parts``.  ``tensors``: the
+    42 of ``ttt_backward`` - the sixteen re-materialisation buffers are not used (None is fine); dW1 .. db2 are carried IN PLACE in
+    the output buffers, which start as copies of the upstream gradients of the final state.  The recompute of the range to be swept
+    next runs on ``pipeline.side_stream`` into one of two slot workspaces while the caller's stream sweeps the current range; events
+    order a sweep behind its recompute and a recompute behind the sweep that last read its workspace; the side stream is joined into
+    the caller's stream before this returns (so the workspaces, allocated on the caller's stream, are not reused before it is done)."""
+    from ttt_amd.models.ssm.pipeline import side_stream
+    XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c = tensors[:10]
+    up, dOut, (d_lnw, d_lnb), d_state, (d_eta, dQ, dK, dV) = tensors[27:31], tensors[31], tensors[32:34], tensors[34:38], tensors[38:42]
+    B, NH, NC, CS, F = XQ.shape
+    dev = XQ.device
+    ranges = part_ranges(math.ceil(NC / G), gpp)
+    nbytes = ext.mlp_backward_parts_slots(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl="mfma")
+    slots = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(min(2, len(ranges)))]
+    carry = torch.empty(ext.mlp_backward_parts_carry(B, NH, NC, CS, F, G, XQ.dtype, impl="mfma") // 4, dtype=_F32, device=dev)
+    for d, u in zip(d_state, up):
+        d.copy_(u)
+    main, side = torch.cuda.current_stream(dev), side_stream(dev)
+    rec_args = (None, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c) + (None,) * 32
+    sweep_args = (XQ, XK, XV, last_eta, ln_w, ln_b) + (None,) * 21 + (*d_state, dOut, d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV)
+    ready = [torch.cuda.Event() for _ in ranges]        # recompute of range n is done
+    swept = [torch.cuda.Event() for _ in ranges]        # sweep of range n is done: its workspace may be reused
+
+    def recompute(n):
+        with torch.cuda.stream(side):
+            if n >= 2:
+                side.wait_event(swept[n - 2])
+            ext.ttt_recompute_groups(*rec_args, G, *ranges[n], slots[n & 1], impl="mfma")
+            ready[n].record(side)
+
+    side.wait_stream(main)                              # the inputs, the checkpoints and the workspaces are the caller's stream's
+    recompute(0)
+    for n, (k0, nk) in enumerate(ranges):
+        if n + 1 < len(ranges):
+            recompute(n + 1)
+        main.wait_event(ready[n])
+        ext.ttt_sweep_groups(*sweep_args, G, k0, nk, slots[n & 1], carry, impl="mfma")
+        swept[n].record(main)
+    main.wait_stream(side)
 
 
 def _scan_pair_applies(ext, XQ, G):
@@ -82,10 +137,30 @@ class TkMLP(torch.autograd.Function):
         value = _check_cs16_bwd_impl(TkMLP.cs16_bwd_impl)
         return "mfma" if value == "mfma" and CS == 16 and F == 64 and act_dtype == _BF16 else None
 
+    # That MFMA backward in parts: 0 = one call (default), n > 0 = ranges of n checkpoint groups, the recompute of the next range on
+    # the pipeline's side stream beside the reverse walk of the current one (``backward_in_parts``).  Applies only where ``bwd_impl``
+    # returns "mfma" (so ``cs16_bwd_impl`` must be "mfma" too); ignored everywhere else.  Same bits either way.  Default from the
+    # environment variable TTT_MLP_CS16_BACKWARD_PARTS, read once at import.
+    cs16_backward_parts = _cs16_backward_parts_default()
+
+    @staticmethod
+    def bwd_parts(impl):
+        """checkpoint groups per part for a backward whose ``bwd_impl`` is ``impl``: 0 = the one call"""
+        gpp = TkMLP.cs16_backward_parts
+        if not isinstance(gpp, int) or isinstance(gpp, bool) or gpp < 0:
+            raise ValueError(f"TkMLP.cs16_backward_parts: expected a non-negative integer, got {gpp!r}")
+        return gpp if impl == "mfma" else 0
+
     @staticmethod
     def bwd_call(ext, impl):
-        """the binding's backward for that ``impl``: ``ttt_backward`` itself unless the switch applies"""
-        return ext.ttt_backward if impl is None else functools.partial(ext.ttt_backward_impl, impl)
+        """the binding's backward for that ``impl``: ``ttt_backward`` itself unless the switch applies; in parts where
+        ``cs16_backward_parts`` applies too (same 42 tensors + G)"""
+        if impl is None:
+            return ext.ttt_backward
+        gpp = TkMLP.bwd_parts(impl)
+        if gpp:
+            return lambda *a: backward_in_parts(ext, gpp, a[:-1], a[-1])
+        return functools.partial(ext.ttt_backward_impl, impl)
 
     @staticmethod
     def forward(ctx, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W2_init, b2_init,
@@ -128,8 +203,10 @@ class TkMLP(torch.autograd.Function):
         up = (z32(B, NH, F, H), z32(B, NH, 1, H), z32(B, NH, H, F), z32(B, NH, 1, F))  # final state is not an output
         g_out = grad_out.to(_BF16).contiguous()
         out = g_out                 # placeholder for the ABI's XQW slot (mlp_tk.py:236): same shape / dtype, never read
-        # re-materialisation scratch, shapes/dtypes of mlp_tk.py:192-210
-        remat = (e32(B, NH, G, F, H), e32(B, NH, G, 1, H), e32(B, NH, G, H, F), e32(B, NH, G, 1, F),
+        # re-materialisation scratch, shapes/dtypes of mlp_tk.py:192-210 (the backward in parts keeps its state in its own workspaces)
+        impl = TkMLP.bwd_impl(CS, F, XQ.dtype)
+        remat = (None,) * 16 if TkMLP.bwd_parts(impl) else (
+                 e32(B, NH, G, F, H), e32(B, NH, G, 1, H), e32(B, NH, G, H, F), e32(B, NH, G, 1, F),
                  e16(B, NH, G, CS, F), e32(B, NH, G, CS, 1),
                  e16(B, NH, G, CS, H), e16(B, NH, G, CS, H), e16(B, NH, G, CS, H), e16(B, NH, G, CS, H),
                  e16(B, NH, G, CS, F), e16(B, NH, G, CS, H), e16(B, NH, G, CS, F), e16(B, NH, G, CS, F), e16(B, NH, G, CS, F),
@@ -139,8 +216,8 @@ class TkMLP(torch.autograd.Function):
         d_eta = torch.empty(B, NH, NC, CS, 1, device=dev, dtype=_BF16)
         dQ, dK, dV = (torch.empty_like(XQ) for _ in range(3))
 
-        TkMLP.bwd_call(ext, TkMLP.bwd_impl(CS, F, XQ.dtype))(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c, out, *remat, *up,
-                                                              g_out, d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
+        TkMLP.bwd_call(ext, impl)(XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c, out, *remat, *up,
+                                   g_out, d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV, G)
 
         ln_dt, st_dt = ctx.param_dtypes
         d_lnw = d_lnw.sum(dim=0).squeeze(1).to(ln_dt)

@@ -1185,5 +1185,418 @@ TTT_WV_FN void sweep_groups(BK& bk, const Lin16BwdPartParams& q, int bh) {
     if (k0 == 0) store_ln_grads(bk, p, bh, y);
 }
 
+// ===================================================================================================================
+// A third stage of the backward in parts (Lin16BwdFrontParams, ttt_wave_types.h).  Of a reverse step, the blocks (2), (4) and (1)
+// depend on the step's tiles and on the slots alone, not on the carried gradients: like the recompute they can run for every step of
+// a range at once.  front_groups does that, one wave per (b, h, step): it stores the step's dXQ and leaves a RECORD of what the rest
+// of the step takes from those blocks; chain_groups is the walk that remains - (3), (6), (8), (5/7/9), (10) - reading the records.
+// front_step + chain_step are the statements of reverse_step, in its order per carried variable, so the bits are the one call's.
+// A record: REC_FIELDS 16-byte fields per lane, field-major ([field][lane][16 bytes]: a wave's access to a field is contiguous).
+constexpr int REC_DZB = 0;       // 2 fields: dZbp[0..3] (bf16x4 each)
+constexpr int REC_CSUM = 2;      // colsum16(dzb)[fb]: the addends of db1
+constexpr int REC_DGAM = 3, REC_DBET = 4;     // the addends of block (2) to the dgamma / dbeta partial sums, [fb]
+constexpr int REC_XH = 5, REC_GO = 9, REC_GZ = 13;       // InnerGrad: 4 fields each
+constexpr int REC_RSTD = 17, REC_S2G = 18;
+constexpr int REC_FIELDS = 19;
+static_assert(LIN_FRONT_RECORD_BYTES == (size_t)REC_FIELDS * 64 * 16, "a step record of the backward's front");
+
+template <class BK, class T>
+TTT_WV_FN void st_rec(BK& bk, char* rec, int idx, T v) {
+    static_assert(sizeof(T) == 16, "a record field");
+    *reinterpret_cast<T*>(rec + ((size_t)idx * 64 + bk.lane()) * 16) = v;
+}
+TTT_WV_FN f32x4 vec4(const float (&v)[4]) { f32x4 r = {v[0], v[1], v[2], v[3]}; return r; }
+
+// inner_grad for front_step.  In the walk kernels the compiled inner_grad sums the four products gxh[fb] = go[fb] gamma[fb] of a row as
+// fma(go1, gamma1, gxh0) and fuses on from there; on its own in the front kernel the compiler rounds gxh1 and fuses gxh0 instead.  So
+// the sums of products - and, with them, the remaining expressions where a product meets an add - are written out with fma4 the way
+// the walk kernels' code takes them.  (On the host a sum of rounded products either way: same bits.)
+template <class BK>
+TTT_WV_FN void inner_grad_pinned(BK& bk, const f32x4 (&z)[4], const f32x4 (&tg)[4], const float (&gam)[4], const float (&bet)[4], float eps,
+                                 InnerGrad& o) {
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) o.xh[fb] = z[fb];
+    o.rstd = normalize_rows(bk, o.xh, eps);
+    f32x4 gxh[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        o.go[fb] = fma4(splat4(gam[fb]), o.xh[fb], splat4(bet[fb])) - tg[fb];
+        gxh[fb] = o.go[fb] * gam[fb];
+    }
+    f32x4 s1 = fma4(o.go[1], splat4(gam[1]), gxh[0]);                     // gxh[0] + gxh[1] + gxh[2] + gxh[3]
+    s1 = fma4(o.go[2], splat4(gam[2]), s1);
+    s1 = fma4(o.go[3], splat4(gam[3]), s1);
+    f32x4 s2 = fma4(o.xh[0], gxh[0], gxh[1] * o.xh[1]);                   // the same sum of gxh[fb] xh[fb]
+    s2 = fma4(o.xh[2], gxh[2], s2);
+    s2 = fma4(o.xh[3], gxh[3], s2);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { s1[r] = bk.sum16(s1[r]); s2[r] = bk.sum16(s2[r]); }
+    o.s2g = s2;
+    const f32x4 sc = o.rstd * (1.0f / 64.0f);
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) o.gz[fb] = fma4(-o.xh[fb], o.s2g, fma4(splat4(64.0f), gxh[fb], -s1)) * sc;
+}
+
+// blocks (2), (4), (1) of reverse_step.  Tiles of the step at Kt, Vt, Qt, Dt ; slot / b1v: the state entering the step, slot_n / b1n:
+// the state after it ; dXQ of the step goes to tile `tile`, everything the chain needs to `rec`.
+template <class BK>
+TTT_WV_FN void front_step(BK& bk, const Lin16Params& p, const BwdConsts& c, size_t tile, int Kt, int Vt, int Qt, int Dt, const char* slot,
+                          const char* slot_n, const float (&b1v)[4], const float (&b1n)[4], char* rec) {
+    // ---- (2) outer LayerNorm backward: Z1b = Q W1n + b1n ; dZ1b -----------------------------------------------------------
+    bf16x4 dZbp[4];
+    f32x4 dq[4];                     // starts as dOut (accumulator layout), becomes dQ
+    {
+        const bf16x8 qA0 = rho_read(bk, Qt, 0), qA1 = rho_read(bk, Qt, 32);
+        f32x4 yy[4], dxl[4], t2[4];
+        float addg[4], addb[4], csum[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            f32x4 a = zero4();
+            a = bk.mma32(qA0, ld_pack(bk, slot_n, fb), a);
+            a = bk.mma32(qA1, ld_pack(bk, slot_n, 4 + fb), a);
+            yy[fb] = a + b1n[fb];
+            dq[fb] = bk.mma16(c.IDP, tr4(bk, Dt, TS, 0, 16 * fb), zero4());                     // exact dOut
+        }
+        const f32x4 rstdl = normalize_rows(bk, yy, c.eps);                                    // yy <- x_hat of the output LN
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dx = dq[fb] * yy[fb];
+            addg[fb] = dx[0] + dx[1] + dx[2] + dx[3];
+            addb[fb] = dq[fb][0] + dq[fb][1] + dq[fb][2] + dq[fb][3];
+            dxl[fb] = dq[fb] * c.gam[fb];
+            t2[fb] = dxl[fb] * yy[fb];
+        }
+        const f32x4 u1 = rowsum64(bk, dxl), u2 = rowsum64(bk, t2);
+        const f32x4 sc = rstdl * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dzb = (64.0f * dxl[fb] - u1 - yy[fb] * u2) * sc;
+            dZbp[fb] = pack4(dzb);
+            csum[fb] = colsum16(bk, dzb);
+        }
+        st_rec(bk, rec, REC_DZB, cat(dZbp[0], dZbp[1]));
+        st_rec(bk, rec, REC_DZB + 1, cat(dZbp[2], dZbp[3]));
+        st_rec(bk, rec, REC_CSUM, vec4(csum));
+        st_rec(bk, rec, REC_DGAM, vec4(addg));
+        st_rec(bk, rec, REC_DBET, vec4(addb));
+    }
+    // ---- (4) dQ = dOut + dZ1b W1n^T ------------------------------------------------------------------------------------------------
+    {
+        bf16x8 aZ[2];
+        image_of(bk, L_IMG, dZbp, aZ);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dq[fa] = bk.mma32(aZ[0], ld_pack(bk, slot_n, 8 + fa), dq[fa]);
+            dq[fa] = bk.mma32(aZ[1], ld_pack(bk, slot_n, 12 + fa), dq[fa]);
+        }
+        store_rows(bk, L_IMG + IMG_BYTES, dq, p.dXQ + tile * 1024);
+    }
+    bk.lds_fence();
+    // ---- (1) inner forward of the step: Z1 = K W + b, LN / L2 gradient ------------------------------------------------
+    const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
+    InnerGrad ig;
+    {
+        f32x4 z[4], tg[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const bf16x4 kT = tr4(bk, Kt, TS, 0, 16 * fb);
+            f32x4 a = zero4();
+            a = bk.mma32(kA0, ld_pack(bk, slot, fb), a);
+            a = bk.mma32(kA1, ld_pack(bk, slot, 4 + fb), a);
+            z[fb] = a + b1v[fb];
+            tg[fb] = bk.mma16(c.IDN, kT, bk.mma16(c.IDP, tr4(bk, Vt, TS, 0, 16 * fb), zero4()));   // exact V - K
+        }
+        inner_grad_pinned(bk, z, tg, c.gam, c.bet, c.eps, ig);
+    }
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        st_rec(bk, rec, REC_XH + fb, ig.xh[fb]);
+        st_rec(bk, rec, REC_GO + fb, ig.go[fb]);
+        st_rec(bk, rec, REC_GZ + fb, ig.gz[fb]);
+    }
+    st_rec(bk, rec, REC_RSTD, ig.rstd);
+    st_rec(bk, rec, REC_S2G, ig.s2g);
+}
+
+// wave `unit` = bh * (steps of the range) + j runs the front of step k0 * G + j of (b, h) = bh, from the slots recompute_groups left
+// for the same range: dXQ of the step and its record.  The tiles are parked once, in buffer 0 of their kind.
+template <class BK>
+TTT_WV_FN void front_groups(BK& bk, const Lin16BwdFrontParams& f, int unit) {
+    const Lin16BwdPartParams& q = f.q;
+    const Lin16Params& p = q.p;
+    const int NC = p.NC, G = p.G;
+    const int s_lo = q.k0 * G, s_hi = ((q.k0 + q.nk) * G < NC) ? (q.k0 + q.nk) * G : NC, ns = s_hi - s_lo;
+    const int bh = unit / ns, it = s_lo + unit % ns, k = it / G, lo = k * G, head = bh % p.NH;
+    const int i = bk.lane() & 15;
+    const size_t tile = (size_t)bh * NC + it;
+    const size_t cell = (size_t)bh * q.nk + (k - q.k0);                                             // (b, h, group of the range)
+    const char* slot = q.slots + (cell * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;                // state entering the step
+    const char* slot_n = slot + LIN_PART_SLOT_BYTES;                                                // ... and after it
+    char* rec = f.records + (cell * G + (it - lo)) * LIN_FRONT_RECORD_BYTES;
+
+    BwdConsts c;
+    bwd_consts(bk, p, head, c);
+    Stage sk, sv, sq, sd;
+    stage_request(bk, sk, p.XK + tile * 1024);
+    stage_request(bk, sv, p.XV + tile * 1024);
+    stage_request(bk, sq, p.XQ + tile * 1024);
+    stage_request(bk, sd, p.dOut + tile * 1024);
+    float b1v[4], b1n[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        b1v[fb] = reinterpret_cast<const float*>(slot + SLOT_BYTES)[16 * fb + i];
+        b1n[fb] = reinterpret_cast<const float*>(slot_n + SLOT_BYTES)[16 * fb + i];
+    }
+    stage_park(bk, sk, L_K); stage_park(bk, sv, L_V); stage_park(bk, sq, L_Q); stage_park(bk, sd, L_D);
+    bk.lds_fence();
+    front_step(bk, p, c, tile, L_K, L_V, L_Q, L_D, slot, slot_n, b1v, b1n, rec);
+}
+
+// The chain keeps two step records in the wave's LDS behind the transposing image (where backward() keeps the state that ends a group):
+// the record of the step in front is fetched in three batches of fields while a step runs, each held in registers from one hook of
+// chain_step to the next only.
+constexpr int L_REC = L_WHI;
+constexpr int WAVE_LDS_CHAIN = L_REC + 2 * (int)LIN_FRONT_RECORD_BYTES;
+static_assert(WAVE_LDS_CHAIN <= 160 * 1024 && L_REC % 16 == 0, "LDS budget");
+constexpr int REC_B0 = 0, REC_N0 = 7, REC_B1 = 7, REC_N1 = 6, REC_B2 = 13, REC_N2 = 6;       // the batches: first field, fields
+static_assert(REC_B0 + REC_N0 == REC_B1 && REC_B1 + REC_N1 == REC_B2 && REC_B2 + REC_N2 == REC_FIELDS, "the batches cover a record");
+
+template <int F0, int N, class BK>
+TTT_WV_FN void rec_request(BK& bk, int l, const char* rec, u32x4 (&r)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) r[j] = *reinterpret_cast<const u32x4*>(rec + ((size_t)(F0 + j) * 64 + l) * 16);
+}
+template <int F0, int N, class BK>
+TTT_WV_FN void rec_park(BK& bk, int l, int rec_off, const u32x4 (&r)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) bk.template lds<u32x4>(rec_off + ((F0 + j) * 64 + l) * 16) = r[j];
+}
+
+// reverse_step without its blocks (2), (4), (1): their results come from the step's record, in LDS at rec_off.  Tiles of the step at
+// Kt, Qt, eta at eta_off ; slot: the state entering the step (its transposed packs 8..15 only).  h0 / h1 / h2 run after (3), after (8)
+// and after (10): where the caller moves what it fetches for the step in front.  The caller fences LDS behind the step.
+template <class BK, class H0, class H1, class H2>
+TTT_WV_FN void chain_step(BK& bk, int l, const Lin16Params& p, const BwdConsts& c, BwdCarry& y, size_t tile, int Kt, int Qt, int eta_off,
+                          const char* slot, int rec_off, H0&& h0, H1&& h1, H2&& h2) {
+    const int g = l >> 4, i = l & 15;
+    const f32x4 eta4 = bk.template lds<f32x4>(eta_off + 4 * g * 4);
+    const int ro = rec_off + l * 16;                  // this lane's cell of field 0
+    // ---- what (2) adds to the carry ----------------------------------------------------------------------------------------------
+    {
+        const f32x4 addg = bk.template lds<f32x4>(ro + REC_DGAM * 1024), addb = bk.template lds<f32x4>(ro + REC_DBET * 1024);
+        const f32x4 csum = bk.template lds<f32x4>(ro + REC_CSUM * 1024);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            y.dgam[fb] += addg[fb];
+            y.dbet[fb] += addb[fb];
+        }
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) y.db[fb] += csum[fb];                                   // db1n += colsum dZ1b (fp32)
+    }
+    // ---- (3) dW1n += Q^T dZ1b ; db1n += colsum dZ1b ------------------------------------------------------------------------------
+    {
+        const bf16x8 d01 = bk.template lds<bf16x8>(ro + REC_DZB * 1024), d23 = bk.template lds<bf16x8>(ro + (REC_DZB + 1) * 1024);
+        const bf16x4 dZbp[4] = {__builtin_shufflevector(d01, d01, 0, 1, 2, 3), __builtin_shufflevector(d01, d01, 4, 5, 6, 7),
+                                __builtin_shufflevector(d23, d23, 0, 1, 2, 3), __builtin_shufflevector(d23, d23, 4, 5, 6, 7)};
+        bf16x4 qT[4];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) qT[fa] = tr4(bk, Qt, TS, 0, 16 * fa);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+#pragma unroll
+            for (int fa = 0; fa < 4; ++fa) y.dWt[fa][fb] = bk.mma16(qT[fa], dZbp[fb], y.dWt[fa][fb]);
+        }
+    }
+    h0();
+    const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
+    bf16x4 kT[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) kT[fb] = tr4(bk, Kt, TS, 0, 16 * fb);
+    const f32x4 ig_rstd = bk.template lds<f32x4>(ro + REC_RSTD * 1024);
+    // ---- (6) dgZ1 = -eta (K dW1n + db1n) ; (8) backward of the fused LN / L2 gradient -> dZ1, dt, dgamma, dbeta -----------------
+    bf16x4 dZ1p[4];
+    float dbz[4];                        // colsum dZ1 (fp32), added to db1 in (10) - d(eta) in (7) needs db1n
+    f32x4 dk[4];                     // starts as -dt (dt = gradient w.r.t. the target V - K = dV)
+    {
+        f32x4 dgz[4], mGr[4], t2[4], xh[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            xh[fb] = bk.template lds<f32x4>(ro + (REC_XH + fb) * 1024);
+            f32x4 a = zero4();
+            a = bk.mma32(kA0, stack(y.dWt[0][fb], y.dWt[1][fb]), a);
+            a = bk.mma32(kA1, stack(y.dWt[2][fb], y.dWt[3][fb]), a);
+            dgz[fb] = (a + y.db[fb]) * (-eta4);
+            mGr[fb] = dgz[fb] * (-ig_rstd);
+            t2[fb] = mGr[fb] * xh[fb];
+        }
+        const f32x4 s1 = rowsum64(bk, mGr) * (1.0f / 64.0f), s2 = rowsum64(bk, t2) * (1.0f / 64.0f);
+        const f32x4 c2 = bk.template lds<f32x4>(ro + REC_S2G * 1024) * (1.0f / 64.0f);
+        f32x4 dxh[4], dstd[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 go = bk.template lds<f32x4>(ro + (REC_GO + fb) * 1024), gz = bk.template lds<f32x4>(ro + (REC_GZ + fb) * 1024);
+            const f32x4 dgxh = fma4(dgz[fb], ig_rstd, s1) + xh[fb] * s2;
+            const f32x4 dy = dgxh * c.gam[fb];
+            const f32x4 dg = fma4(go, dgxh, dy * xh[fb]);
+            y.dgam[fb] += dg[0] + dg[1] + dg[2] + dg[3];
+            y.dbet[fb] += dy[0] + dy[1] + dy[2] + dy[3];
+            dk[fb] = dy;                                                                       // = -dt
+            dxh[fb] = fma4(go * c.gam[fb], s2, dy * c.gam[fb]) + mGr[fb] * c2;
+            dstd[fb] = fma4(dgz[fb], gz, dxh[fb] * xh[fb]) * (-ig_rstd);
+        }
+        const f32x4 v1 = rowsum64(bk, dxh) * (1.0f / 64.0f), v2 = rowsum64(bk, dstd) * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dz1 = fma4(dxh[fb] - v1, ig_rstd, xh[fb] * v2);
+            dZ1p[fb] = pack4(dz1);
+            dbz[fb] = colsum16(bk, dz1);
+        }
+        f32x4 dv[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) dv[fb] = -dk[fb];
+        store_rows(bk, L_IMG + IMG_BYTES, dv, p.dXV + tile * 1024);                              // dV = dt
+    }
+    h1();
+    bk.lds_fence();
+    // ---- (5, 7, 9) A1 = gZ1 dW1n^T ; d eta ; dK = -eta A1 - dt + dZ1 W^T --------------------------------------------------------------
+    {
+        bf16x8 dWT[2][4];
+        transposed_packs(bk, y.dWt, dWT);
+        f32x4 gz[4];
+        bf16x4 gzq[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            gz[fb] = bk.template lds<f32x4>(ro + (REC_GZ + fb) * 1024);
+            gzq[fb] = pack4(gz[fb]);
+        }
+        bf16x8 aG[2];
+        image_of(bk, L_IMG, gzq, aG);
+        f32x4 acc[4];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            f32x4 a1 = zero4();
+            a1 = bk.mma32(aG[0], dWT[0][fa], a1);
+            a1 = bk.mma32(aG[1], dWT[1][fa], a1);
+            dk[fa] -= a1 * eta4;
+            const f32x4 kc = bk.mma16(c.IDP, kT[fa], zero4());                                  // exact K, accumulator layout
+            acc[fa] = fma4(gz[fa], splat4(y.db[fa]), kc * a1);
+        }
+        const f32x4 de = rowsum64(bk, acc);
+        if (i == 0) *reinterpret_cast<bf16x4*>(p.deta + tile * 16 + 4 * g) = pack4(-de);
+    }
+    bk.lds_fence();
+    {
+        bf16x8 aD[2];
+        image_of(bk, L_IMG, dZ1p, aD);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dk[fa] = bk.mma32(aD[0], ld_pack(bk, slot, 8 + fa), dk[fa]);
+            dk[fa] = bk.mma32(aD[1], ld_pack(bk, slot, 12 + fa), dk[fa]);
+        }
+        store_rows(bk, L_IMG + IMG_BYTES, dk, p.dXK + tile * 1024);
+    }
+    // ---- (10) dW1 = dW1n + K^T dZ1 ; db1 = db1n + colsum dZ1 --------------------------------------------------------------------------------
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        y.db[fb] += dbz[fb];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) y.dWt[fa][fb] = bk.mma16(kT[fa], dZ1p[fb], y.dWt[fa][fb]);
+    }
+    h2();
+}
+
+// the walk of (b, h) = bh over the groups k0 + nk - 1 .. k0 from the slots recompute_groups and the records front_groups left: the
+// loop and the carry contract of sweep_groups (dW1_last / db1_last -> dW1 / db1, which may alias ; ln_carry ; dln_w / dln_b in the
+// range with k0 == 0) around chain_step.  K, Q, eta and the record of the step in front are fetched while a step runs - none of their
+// addresses depends on the carry - into the LDS buffers of the other parity.
+template <class BK>
+TTT_WV_FN void chain_groups(BK& bk, const Lin16BwdFrontParams& f, int bh) {
+    const Lin16BwdPartParams& q = f.q;
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane();
+    const int NC = p.NC, G = p.G, K = p.K, head = bh % p.NH;
+    const int k0 = q.k0, nk = q.nk;
+    const int s_lo = k0 * G, s_hi = ((k0 + nk) * G < NC) ? (k0 + nk) * G : NC;      // the steps [s_lo, s_hi)
+    const size_t tile0 = (size_t)bh * NC;
+    const char* slots = q.slots + (size_t)bh * nk * (G + 1) * LIN_PART_SLOT_BYTES;
+    const char* recs = f.records + (size_t)bh * nk * G * LIN_FRONT_RECORD_BYTES;
+    float* carry = q.ln_carry + (size_t)bh * LIN_PART_CARRY_FLOATS * 64 + l0;
+
+    BwdConsts c;
+    BwdCarry y;
+    load_matrix(bk, p.dW1_last + (size_t)bh * 64 * 64, y.dWt);
+    load_row(bk, p.db1_last + (size_t)bh * 64, y.db);
+    bwd_consts(bk, p, head, c);
+    if (k0 + nk == K) {      // the range that ends the sequence starts the sums
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) y.dgam[fb] = y.dbet[fb] = 0.f;
+    } else {
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) { y.dgam[fb] = carry[fb * 64]; y.dbet[fb] = carry[(4 + fb) * 64]; }
+    }
+    int k = k0 + nk - 1, lo = k * G;          // the group of step `it`
+    Stage sk, sq;
+    unsigned short pe = 0;
+    u32x4 r0[REC_N0], r1[REC_N1], r2[REC_N2];
+    {   // the first step of the walk
+        const int s0 = s_hi - 1, o = (s0 & 1) * TILE * 2, ro = L_REC + (s0 & 1) * (int)LIN_FRONT_RECORD_BYTES;
+        const char* rec = recs + ((size_t)(k - k0) * G + (s0 - lo)) * LIN_FRONT_RECORD_BYTES;
+        stage_request(bk, sk, p.XK + (tile0 + s0) * 1024);
+        stage_request(bk, sq, p.XQ + (tile0 + s0) * 1024);
+        pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + s0) * 16 + (l0 & 15));
+        stage_park(bk, sk, L_K + o); stage_park(bk, sq, L_Q + o);
+        park_eta(bk, l0, pe, L_ETA + (s0 & 1) * 64);
+        rec_request<REC_B0, REC_N0>(bk, l0, rec, r0); rec_park<REC_B0, REC_N0>(bk, l0, ro, r0);
+        rec_request<REC_B1, REC_N1>(bk, l0, rec, r1); rec_park<REC_B1, REC_N1>(bk, l0, ro, r1);
+        rec_request<REC_B2, REC_N2>(bk, l0, rec, r2); rec_park<REC_B2, REC_N2>(bk, l0, ro, r2);
+        bk.lds_fence();
+    }
+    for (int it = s_hi - 1; it >= s_lo; --it) {
+        if (it < lo) { --k; lo -= G; }
+        const int buf = it & 1, nb = buf ^ 1;
+        const int l = bk.opaque(l0);
+        const bool more = it > s_lo;
+        const char* rec_n = recs;
+        const int ro_n = L_REC + nb * (int)LIN_FRONT_RECORD_BYTES;
+        if (more) {
+            const int kn = (it - 1 < lo) ? k - 1 : k, lon = (it - 1 < lo) ? lo - G : lo;      // the group of the step in front
+            rec_n = recs + ((size_t)(kn - k0) * G + (it - 1 - lon)) * LIN_FRONT_RECORD_BYTES;
+            stage_request(bk, sk, p.XK + (tile0 + it - 1) * 1024);
+            stage_request(bk, sq, p.XQ + (tile0 + it - 1) * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + (tile0 + it - 1) * 16 + (l & 15));
+            rec_request<REC_B0, REC_N0>(bk, l, rec_n, r0);
+        }
+        const char* slot = slots + ((size_t)(k - k0) * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;       // state entering the step
+        chain_step(bk, l, p, c, y, tile0 + it, L_K + buf * TILE * 2, L_Q + buf * TILE * 2, L_ETA + buf * 64, slot,
+                   L_REC + buf * (int)LIN_FRONT_RECORD_BYTES,
+                   [&] {
+                       if (more) {
+                           stage_park(bk, sk, L_K + nb * TILE * 2); stage_park(bk, sq, L_Q + nb * TILE * 2);
+                           park_eta(bk, l, pe, L_ETA + nb * 64);
+                           rec_park<REC_B0, REC_N0>(bk, l, ro_n, r0);
+                           rec_request<REC_B1, REC_N1>(bk, l, rec_n, r1);
+                       }
+                   },
+                   [&] {
+                       if (more) {
+                           rec_park<REC_B1, REC_N1>(bk, l, ro_n, r1);
+                           rec_request<REC_B2, REC_N2>(bk, l, rec_n, r2);
+                       }
+                   },
+                   [&] {
+                       if (more) rec_park<REC_B2, REC_N2>(bk, l, ro_n, r2);
+                   });
+        bk.lds_fence();
+    }
+    // ---- hand-over, as in sweep_groups: q.p.dW1 / db1 may alias dW1_last / db1_last ; ln_carry is read and written by the same lane
+    store_matrix(bk, p.dW1 + (size_t)bh * 64 * 64, y.dWt);
+    if ((l0 >> 4) == 0)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) p.db1[(size_t)bh * 64 + 16 * fb + (l0 & 15)] = y.db[fb];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) { carry[fb * 64] = y.dgam[fb]; carry[(4 + fb) * 64] = y.dbet[fb]; }
+    if (k0 == 0) store_ln_grads(bk, p, bh, y);
+}
+
 }  // namespace lin16
 }  // namespace ttt

@@ -157,6 +157,21 @@ void linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0
     const wv::Lin16BwdPartParams q = {linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry};
     launch_linear_sweep_groups(q, d->CS, d->B * d->NH, s);
 }
+// The third stage at mini-batches of 16 (ttt_wave_types.h: Lin16BwdFrontParams): one record per step of the range.
+size_t linear_backward_front_records(const ttt_dims* d, int nk) {
+    return (size_t)d->B * d->NH * (size_t)nk * (size_t)d->G * wv::LIN_FRONT_RECORD_BYTES;
+}
+void linear_front_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, void* records, hipStream_t s) {
+    const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), nullptr}, (char*)records};
+    const int s_hi = (k0 + nk) * d->G < d->NC ? (k0 + nk) * d->G : d->NC;
+    launch_linear_front_groups(f, d->B * d->NH * (s_hi - k0 * d->G), s);
+}
+void linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, const void* records,
+                         float* ln_carry, hipStream_t s) {
+    const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry},
+                                       (char*)const_cast<void*>(records)};
+    launch_linear_chain_groups(f, d->B * d->NH, s);
+}
 
 }  // namespace mfma
 }  // namespace ttt

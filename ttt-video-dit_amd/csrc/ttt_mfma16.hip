@@ -280,6 +280,20 @@ __global__ __launch_bounds__(64 * lin64::WAVES) void linear_sweep_cs64_groups_ke
     lin64::sweep_groups(bk, q, blockIdx.x);
 }
 
+// A third stage of the backward in parts at mini-batches of 16 (lin16::front_groups, chain_groups): the half of every reverse step
+// that does not depend on the carried gradients, one wave per (b, h, step of the range), and the walk that consumes its records,
+// one wave per (b, h).
+__global__ __launch_bounds__(64) void linear_front16_groups_kernel(wv::Lin16BwdFrontParams f) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin16::front_groups(bk, f, blockIdx.x);
+}
+__global__ __launch_bounds__(64) void linear_chain16_groups_kernel(wv::Lin16BwdFrontParams f) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    DeviceWave bk{smem};
+    lin16::chain_groups(bk, f, blockIdx.x);
+}
+
 }  // namespace v16
 
 static void lin_attr_once() {
@@ -333,6 +347,22 @@ void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_b
     lin_parts_attr_once();
     if (cs == 16) hipLaunchKernelGGL(v16::linear_sweep16_groups_kernel, dim3(n_bh), dim3(64), lin16::L_WHI, s, q);
     else hipLaunchKernelGGL(v16::linear_sweep_cs64_groups_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::L_WHI, s, q);
+}
+
+static void lin_front_attr_once() {
+    static ttt::OncePerDevice done;
+    done.run([&] {
+        (void)hipFuncSetAttribute((const void*)v16::linear_front16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS);
+        (void)hipFuncSetAttribute((const void*)v16::linear_chain16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS_CHAIN);
+    });
+}
+void launch_linear_front_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s) {
+    lin_front_attr_once();
+    hipLaunchKernelGGL(v16::linear_front16_groups_kernel, dim3(n_units), dim3(64), lin16::WAVE_LDS, s, f);
+}
+void launch_linear_chain_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s) {
+    lin_front_attr_once();
+    hipLaunchKernelGGL(v16::linear_chain16_groups_kernel, dim3(n_bh), dim3(64), lin16::WAVE_LDS_CHAIN, s, f);
 }
 
 void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*, hipStream_t s) {

@@ -62,6 +62,9 @@ void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t
 // TTT-Linear backward in parts at mini-batches `cs` = 16 / 64: recompute grid n_bh * q.nk, sweep grid n_bh
 void launch_linear_recompute_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s);
 void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s);
+// ... and its third stage at mini-batches of 16: front grid n_units = n_bh * (steps of the range), chain grid n_bh
+void launch_linear_front_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s);
+void launch_linear_chain_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s);
 void set_debug_dump(float* buf);
 unsigned long long* get_debug_timing();
 void set_debug_overlap_tail(int v);   // backward schedule: 0 one stream, 1 tail of chunk c beside the sweep of chunk c-1, 2 (default) the next recompute too

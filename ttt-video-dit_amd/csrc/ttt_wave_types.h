@@ -60,6 +60,18 @@ struct Lin16BwdPartParams {
     float* ln_carry;
 };
 
+// a third stage of the TTT-Linear backward in parts, mini-batches of 16 only (ttt_lin16_body.h: front_groups, chain_groups): the half
+// of every reverse step that does not depend on the carried gradients runs for all steps of the range `q` at once and leaves, per
+// step, a record of LIN_FRONT_RECORD_BYTES for the walk: per lane dZ1b as bf16 (32 bytes), its column sums (16), the addends of the
+// dgamma / dbeta partial sums (32), the inner LayerNorm's x_hat, output gradient and dZ1 (192), 1/std and sum_f (go gamma) x_hat (32).
+// `records`: [B*NH][nk][G] records (a ragged last group uses fewer) ; q.slots: what recompute_groups left for the same range ;
+// front_groups does not touch q.ln_carry.
+constexpr size_t LIN_FRONT_RECORD_BYTES = 64 * (32 + 16 + 32 + 192 + 32);      // 19 456
+struct Lin16BwdFrontParams {
+    Lin16BwdPartParams q;
+    char* records;
+};
+
 // arguments of the TTT-MLP forward scan at mini-batches of 16 tokens (F = 64, hidden 256)
 struct Mlp16Params {
     const __bf16 *XQ, *XK, *XV, *eta;

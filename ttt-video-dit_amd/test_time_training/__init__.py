@@ -175,6 +175,14 @@ _PROTOTYPES_MLP_BWD_PARTS = {
     "ttt_hip_mlp_recompute_groups": _sig("2p 2i p z p"),
     "ttt_hip_mlp_sweep_groups": _sig("2p 2i p z p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_lin_bwd_front.h, the sixth header: the carry-free half of the TTT-Linear reverse
+# steps at mini-batches of 16 as a kernel of its own, and the walk that consumes its records (tests/test_abi_lin_bwd_front_cpu.py
+# compares the two)
+_PROTOTYPES_LIN_BWD_FRONT = {
+    "ttt_hip_linear_backward_front_records": _sig("p i", ctypes.c_size_t),
+    "ttt_hip_linear_front_groups": _sig("2p 2i p z p z p"),
+    "ttt_hip_linear_chain_groups": _sig("2p 2i p z p z p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -197,7 +205,7 @@ def load_library() -> ctypes.CDLL:
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
     for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16,
-                                      **_PROTOTYPES_MLP_BWD_PARTS}.items():
+                                      **_PROTOTYPES_MLP_BWD_PARTS, **_PROTOTYPES_LIN_BWD_FRONT}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -649,6 +657,74 @@ def ttt_linear_sweep_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_nor
     if rc != 0:
         raise RuntimeError(lib.ttt_hip_last_error().decode())
     linear_bwd_parts_calls["sweep"] += 1
+
+
+# The third stage of the TTT-Linear backward over ranges of checkpoint groups, mini-batches of 16 (include/ttt_hip_lin_bwd_front.h).
+# The front reads the four activation tiles and the LayerNorm parameters and writes grad_L_XQ; the chain is the sweep without XV,
+# grad_L_XQW and grad_L_XQ.  As above: what a call does not touch may be None, what is given is checked field by field.
+_LIN_FRONT_FIELDS = frozenset(("XQ", "XK", "XV", "ttt_norm_weight", "ttt_norm_bias", "grad_L_XQW", "grad_L_XQ"))
+_LIN_CHAIN_UNUSED = _LIN_SWEEP_UNUSED | frozenset(("XV", "grad_L_XQW", "grad_L_XQ"))
+linear_bwd_front_calls = {"front": 0, "chain": 0}      # launches of this process (tests, tools)
+
+
+def linear_backward_front_records(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of the record workspace of ``ttt_linear_front_groups`` / ``ttt_linear_chain_groups`` for ``nk`` checkpoint groups:
+    B * NH * nk * G records of 19456 bytes ; 0 where CS != 16"""
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(load_library().ttt_hip_linear_backward_front_records(ctypes.byref(d), int(nk)))
+
+
+def ttt_linear_front_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
+                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
+                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
+                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, records):
+    """The half of every reverse step of the checkpoint groups [k0, k0 + nk) that does not depend on the carried gradients, all steps
+    at once, from the ``slots`` ``ttt_linear_recompute_groups`` left for the same range (``ttt_hip_linear_front_groups``,
+    include/ttt_hip_lin_bwd_front.h): writes ``grad_L_XQ`` of those steps and one record per step into ``records``
+    (``linear_backward_front_records`` bytes for nk groups).  The tensor list of ``ttt_linear_backward_impl``; only XQ, XK, XV,
+    grad_L_XQW, the LayerNorm parameters and grad_L_XQ are needed, the rest may be None.  MFMA sweep at mini-batches of 16 only."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
+               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
+               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(LIN_BWD_FIELDS) - _LIN_FRONT_FIELDS)
+    lib = load_library()
+    _device_bytes(slots, "slots")
+    _device_bytes(records, "records")
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_linear_front_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                             slots.numel() * slots.element_size(), _p(records),
+                                             records.numel() * records.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    linear_bwd_front_calls["front"] += 1
+
+
+def ttt_linear_chain_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
+                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
+                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
+                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, records, ln_carry):
+    """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` and the ``records`` of the same range
+    (``ttt_hip_linear_chain_groups``): ``ttt_linear_sweep_groups`` without the work ``ttt_linear_front_groups`` has done - same carries
+    (dW1 / db1 in place, ``ln_carry``), same bits.  XV, grad_L_XQW, grad_L_XQ, the checkpoints and ``*_init_group`` may be None.  The
+    caller orders recompute -> front -> chain of a range (same stream, or events)."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
+               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
+               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
+    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, _LIN_CHAIN_UNUSED)
+    lib = load_library()
+    _device_bytes(slots, "slots")
+    _device_bytes(records, "records")
+    _device_bytes(ln_carry, "ln_carry")
+    if ln_carry.dtype != torch.float32:
+        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_linear_chain_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
+                                             slots.numel() * slots.element_size(), _p(records),
+                                             records.numel() * records.element_size(), _p(ln_carry),
+                                             ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    linear_bwd_front_calls["chain"] += 1
 
 
 # The TTT-MLP backward at mini-batches of 16 over ranges of checkpoint groups (include/ttt_hip_mlp_bwd_parts.h).  The recompute reads

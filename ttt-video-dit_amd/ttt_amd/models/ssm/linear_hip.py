@@ -35,13 +35,24 @@ def _backward_parts_default():
     return int(v)
 
 
-def backward_in_parts(ext, impl, gpp, tensors, G):
+def _backward_front_default():
+    v = os.environ.get("TTT_LINEAR_BACKWARD_FRONT", "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"TTT_LINEAR_BACKWARD_FRONT: expected '0' (off) or '1', got {v!r}")
+    return int(v)
+
+
+def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     """``ttt_linear_backward`` as ranges of ``gpp`` checkpoint groups, walked from the last range to the first (the entries of
     include/ttt_hip_bwd_parts.h).  ``tensors``: the 21 of ``ttt_linear_backward`` - the ``*_init_group`` scratch is not used; dW1 / db1 are
     carried IN PLACE in the output buffers, which start as copies of the upstream gradients of the final state (zeros in
     ``HipLinear.backward``).  The recompute of the range to be swept next runs on ``pipeline.side_stream`` into one of two slot
     workspaces while the caller's stream sweeps the current range; events order a sweep behind its recompute and a recompute behind
-    the sweep that last read its workspace; the side stream is joined into the caller's stream before this returns."""
+    the sweep that last read its workspace; the side stream is joined into the caller's stream before this returns.
+    ``front`` (mini-batches of 16, include/ttt_hip_lin_bwd_front.h): the side stream also runs, behind the recompute of a range, the
+    half of its reverse steps that does not depend on the carried gradients (``ttt_linear_front_groups``, into one of two record
+    workspaces), and the caller's stream walks the range with ``ttt_linear_chain_groups`` instead of the sweep.  Same events: ``ready``
+    is recorded behind the front, ``swept`` guards both workspaces of the range."""
     from ttt_amd.models.ssm.pipeline import side_stream
     (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, uW1, ub1, dOut, _, _, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV) = tensors
     B, NH, NC, CS, F = XQ.shape
@@ -50,6 +61,13 @@ def backward_in_parts(ext, impl, gpp, tensors, G):
     ranges = [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]       # (k0, nk), the last range first
     nbytes = ext.linear_backward_parts_slots(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl)
     slots = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+    if front:
+        rbytes = ext.linear_backward_front_records(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl)
+        records = [torch.empty(rbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        front_args = (XQ, XK, XV, None, ln_w, ln_b, None, None, None, None, dOut) + (None,) * 7 + (dQ, None, None)
+        chain_args = (XQ, XK, None, last_eta, ln_w, ln_b, None, None, dW1, db1, None, None, None, d_lnw, d_lnb, dW1, db1, d_eta, None, dK, dV)
+    else:
+        records = []
     carry = torch.empty(ext.linear_backward_parts_carry(B, NH, NC, CS, F, G, XQ.dtype, impl=impl) // 4, dtype=_F32, device=dev)
     dW1.copy_(uW1); db1.copy_(ub1)
     main, side = torch.cuda.current_stream(dev), side_stream(dev)
@@ -63,17 +81,22 @@ def backward_in_parts(ext, impl, gpp, tensors, G):
             if n >= 2:
                 side.wait_event(swept[n - 2])
             ext.ttt_linear_recompute_groups(impl, *rec_args, G, *ranges[n], slots[n & 1])
+            if front:
+                ext.ttt_linear_front_groups(impl, *front_args, G, *ranges[n], slots[n & 1], records[n & 1])
             ready[n].record(side)
 
     side.wait_stream(main)                              # the inputs, the checkpoints and the workspaces are the caller's stream's
-    for t in slots:
+    for t in slots + records:
         t.record_stream(side)
     recompute(0)
     for n, (k0, nk) in enumerate(ranges):
         if n + 1 < len(ranges):
             recompute(n + 1)
         main.wait_event(ready[n])
-        ext.ttt_linear_sweep_groups(impl, *sweep_args, G, k0, nk, slots[n & 1], carry)
+        if front:
+            ext.ttt_linear_chain_groups(impl, *chain_args, G, k0, nk, slots[n & 1], records[n & 1], carry)
+        else:
+            ext.ttt_linear_sweep_groups(impl, *sweep_args, G, k0, nk, slots[n & 1], carry)
         swept[n].record(main)
     main.wait_stream(side)
 
@@ -89,6 +112,12 @@ class HipLinear(torch.autograd.Function):
     # has at least two ranges and the extension has the entries; every other call is the one call.  Same bits either way.  Default
     # from the environment variable TTT_LINEAR_BACKWARD_PARTS, read once at import.
     backward_parts = _backward_parts_default()
+    # With the backward in parts selected, at mini-batches of 16: 1 = the carry-free half of every reverse step runs as a kernel of its
+    # own beside the recompute (``ttt_linear_front_groups``) and the caller's stream walks the shorter chain (``ttt_linear_chain_groups``),
+    # 0 (default) = the sweep.  Read only where ``backward_parts`` selects the in-parts path and the extension has the entries; every
+    # other call is what it is without it.  Same bits either way.  Default from the environment variable TTT_LINEAR_BACKWARD_FRONT, read
+    # once at import.
+    backward_front = _backward_front_default()
 
     @staticmethod
     def _impl(CS, F, act):
@@ -107,6 +136,13 @@ class HipLinear(torch.autograd.Function):
         if gpp == 0 or math.ceil(NC / G) <= gpp or not hasattr(ext, "ttt_linear_sweep_groups"):
             return False
         return ext.resolved_impl(B, NH, NC, CS, F, G, XQ.dtype, mlp=False, backward=True, impl=impl) == "mfma"
+
+    @staticmethod
+    def _with_front(ext, XQ):
+        v = HipLinear.backward_front
+        if v not in (0, 1) or isinstance(v, bool):
+            raise ValueError(f"HipLinear.backward_front: expected 0 or 1, got {v!r}")
+        return v == 1 and XQ.shape[3] == 16 and hasattr(ext, "ttt_linear_chain_groups")
 
     @staticmethod
     def forward(ctx, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, XQ_batch, XV_batch, XK_batch, eta_batch,
@@ -156,7 +192,7 @@ class HipLinear(torch.autograd.Function):
         tensors = (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
                    d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
         if HipLinear._in_parts(ext, ctx.impl, XQ, G):
-            backward_in_parts(ext, ctx.impl, int(HipLinear.backward_parts), tensors, G)
+            backward_in_parts(ext, ctx.impl, int(HipLinear.backward_parts), tensors, G, front=HipLinear._with_front(ext, XQ))
         else:
             bwd = ext.ttt_linear_backward if ctx.impl is None else (lambda *a: ext.ttt_linear_backward_impl(ctx.impl, *a))
             bwd(*tensors, G)

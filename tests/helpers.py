@@ -182,6 +182,68 @@ def tile_states(d, B):
     return {k: t(d[k]) for k in ("W1", "b1", "W2", "b2") if k in d}
 
 
+# ---- the schedule tests without a device: stand-ins for the two streams and their events ----------------------------------------
+class FakeStream:
+    def __init__(self, name, log):
+        self.name, self.log = name, log
+
+    def wait_stream(self, other):
+        self.log.append(("wait_stream", self.name, other.name))
+
+    def wait_event(self, ev):
+        self.log.append(("wait_event", self.name, ev.n))
+
+
+def fake_streams(monkeypatch):
+    """``torch.cuda.current_stream`` / ``Event`` / ``stream`` and ``pipeline.side_stream`` replaced by stand-ins that write every wait
+    and record to a log -> (log, current): the log, and a one-element list with the name of the stream work is being issued on
+    ("main" / "side"), for a recording extension to read.  Events are numbered in the order they are made."""
+    import contextlib
+    from ttt_amd.models.ssm import pipeline
+    log, current, n_events = [], ["main"], [0]
+    main, side = FakeStream("main", log), FakeStream("side", log)
+
+    class FakeEvent:
+        def __init__(self):
+            self.n = n_events[0]
+            n_events[0] += 1
+
+        def record(self, stream):
+            assert stream.name == current[0], "an event is recorded on the stream its work was issued on"
+            log.append(("record", stream.name, self.n))
+
+    @contextlib.contextmanager
+    def on(stream):
+        old, current[0] = current[0], stream.name
+        try:
+            yield
+        finally:
+            current[0] = old
+
+    monkeypatch.setattr(pipeline, "side_stream", lambda device: side)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: main)
+    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
+    monkeypatch.setattr(torch.cuda, "stream", on)
+    return log, current
+
+
+def count_calls(monkeypatch, e, names):
+    """{label: 0} that counts the calls of the extension's entries ``names`` = {label: attribute} (the TTT-Linear backward's: the
+    plain ``ttt_linear_backward`` is sent through ``ttt_linear_backward_impl``, so that one label counts every one-call backward)"""
+    calls = dict.fromkeys(names, 0)
+
+    def count(label, fn):
+        def wrapped(*a):
+            calls[label] += 1
+            return fn(*a)
+        return wrapped
+
+    for label, attr in names.items():
+        monkeypatch.setattr(e, attr, count(label, getattr(e, attr)))
+    monkeypatch.setattr(e, "ttt_linear_backward", lambda *a: e.ttt_linear_backward_impl(None, *a))
+    return calls
+
+
 class ToyNet(torch.nn.Module):
     """Stand-in for the DiT in sampler tests: nonlinear in x, depends on text and timestep, independent per sample."""
 

@@ -18,23 +18,9 @@ RECOMPUTE_NEEDS = ("XK", "XV", "last_eta", "ttt_norm_weight", "ttt_norm_bias", "
 SWEEP_UNUSED = ("W1_checkpoints", "b1_checkpoints", "W1_init_group", "b1_init_group")
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in the third header (the parser of
-    test_abi_cpu.py, on this file)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
-    protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        assert name not in protos, name
-        params = [] if params.strip() == "void" else params.split(",")
-        protos[name] = (A._c_kind(ret, False), [A._c_kind(p, True) for p in params])
-    assert sorted(protos) == names
-    return protos
-
-
 def test_third_prototype_table_matches_the_third_header():
     import test_time_training as ext
-    declared = _declared_prototypes()
+    declared = A._declared_prototypes(HEADER)
     assert sorted(declared) == sorted(ext._PROTOTYPES_BWD_PARTS)
     assert set(NAMES) <= set(declared)
     for other in (ext._PROTOTYPES, ext._PROTOTYPES_PARTS):

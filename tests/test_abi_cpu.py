@@ -29,15 +29,17 @@ def _c_kind(decl, is_param):
     return _C_KINDS[" ".join(words[:-1] if is_param else words)]
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in include/ttt_hip.h"""
-    src = open(os.path.join(ROOT, "include", "ttt_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+def _declared_prototypes(header_path=os.path.join(ROOT, "include", "ttt_hip.h")):
+    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in a header of the library (default:
+    include/ttt_hip.h; the tests of the other headers call this on theirs); every ``ttt_hip_*(`` of the header must parse"""
+    src = re.sub(r"/\*.*?\*/", "", open(header_path).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
     protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
+    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
         assert name not in protos, name
         params = [] if params.strip() == "void" else params.split(",")
         protos[name] = (_c_kind(ret, False), [_c_kind(p, True) for p in params])
+    assert sorted(protos) == names
     return protos
 
 

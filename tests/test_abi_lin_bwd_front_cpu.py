@@ -19,23 +19,9 @@ FRONT_NEEDS = ("XQ", "XK", "XV", "ttt_norm_weight", "ttt_norm_bias", "grad_L_XQW
 CHAIN_UNUSED = ("W1_checkpoints", "b1_checkpoints", "W1_init_group", "b1_init_group", "XV", "grad_L_XQW", "grad_L_XQ")
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in the sixth header (the parser of
-    test_abi_cpu.py, on this file)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
-    protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        assert name not in protos, name
-        params = [] if params.strip() == "void" else params.split(",")
-        protos[name] = (A._c_kind(ret, False), [A._c_kind(p, True) for p in params])
-    assert sorted(protos) == names
-    return protos
-
-
 def test_sixth_prototype_table_matches_the_sixth_header():
     import test_time_training as ext
-    declared = _declared_prototypes()
+    declared = A._declared_prototypes(HEADER)
     assert sorted(declared) == sorted(ext._PROTOTYPES_LIN_BWD_FRONT) == sorted(NAMES)
     for other in (ext._PROTOTYPES, ext._PROTOTYPES_PARTS, ext._PROTOTYPES_BWD_PARTS, ext._PROTOTYPES_PAIR16, ext._PROTOTYPES_MLP_BWD_PARTS):
         assert not set(ext._PROTOTYPES_LIN_BWD_FRONT) & set(other), "a symbol belongs to one header"

@@ -24,23 +24,9 @@ def _sweep_unused(ext):
     return ("W1_checkpoints", "b1_checkpoints", "W2_checkpoints", "b2_checkpoints", "XQW") + tuple(ext.MLP_BWD_FIELDS[11:27])
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in the fifth header (the parser of
-    test_abi_cpu.py, on this file)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
-    protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        assert name not in protos, name
-        params = [] if params.strip() == "void" else params.split(",")
-        protos[name] = (A._c_kind(ret, False), [A._c_kind(p, True) for p in params])
-    assert sorted(protos) == names
-    return protos
-
-
 def test_fifth_prototype_table_matches_the_fifth_header():
     import test_time_training as ext
-    declared = _declared_prototypes()
+    declared = A._declared_prototypes(HEADER)
     assert sorted(declared) == sorted(ext._PROTOTYPES_MLP_BWD_PARTS) == sorted(NAMES)
     for other in (ext._PROTOTYPES, ext._PROTOTYPES_PARTS, ext._PROTOTYPES_BWD_PARTS, ext._PROTOTYPES_PAIR16):
         assert not set(ext._PROTOTYPES_MLP_BWD_PARTS) & set(other), "a symbol belongs to one header"

@@ -13,27 +13,13 @@ REC_BYTES = 64 * 1024 + 1024 + 256
 FLAG_BYTES = 2 * 128
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in the fourth header (the parser of
-    test_abi_parts_cpu.py, on this file)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
-    protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        assert name not in protos, name
-        params = [] if params.strip() == "void" else params.split(",")
-        protos[name] = (A._c_kind(ret, False), [A._c_kind(p, True) for p in params])
-    assert sorted(protos) == names
-    return protos
-
-
 def _ring():
     return int(re.search(r"^#define TTT_HIP_PAIR16_RING (\d+)\s*$", open(HEADER).read(), flags=re.M).group(1))
 
 
 def test_fourth_prototype_table_matches_the_fourth_header():
     import test_time_training as ext
-    declared = _declared_prototypes()
+    declared = A._declared_prototypes(HEADER)
     assert sorted(declared) == sorted(ext._PROTOTYPES_PAIR16) == ["ttt_hip_mlp_forward_chunk_pair16", "ttt_hip_mlp_forward_pair16_workspace"]
     others = {**ext._PROTOTYPES, **ext._PROTOTYPES_PARTS, **ext._PROTOTYPES_BWD_PARTS}
     assert not set(ext._PROTOTYPES_PAIR16) & set(others), "a symbol belongs to one header"

@@ -11,23 +11,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ttt_hip_parts.h")
 
 
-def _declared_prototypes():
-    """{symbol: (return kind, [parameter kinds])} of every ttt_hip_* function declared in the second header (the parser of
-    test_abi_cpu.py, on this file)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(ttt_hip_\w+)\s*\(", src)))
-    protos = {}
-    for ret, name, params in re.findall(r"(?:^|[;}{])\s*((?:const\s+)?\w+[\s*]+)(ttt_hip_\w+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        assert name not in protos, name
-        params = [] if params.strip() == "void" else params.split(",")
-        protos[name] = (A._c_kind(ret, False), [A._c_kind(p, True) for p in params])
-    assert sorted(protos) == names
-    return protos
-
-
 def test_second_prototype_table_matches_the_second_header():
     import test_time_training as ext
-    declared = _declared_prototypes()
+    declared = A._declared_prototypes(HEADER)
     assert sorted(declared) == sorted(ext._PROTOTYPES_PARTS) == ["ttt_hip_linear_forward_chunk"]
     assert not set(ext._PROTOTYPES_PARTS) & set(ext._PROTOTYPES), "a symbol belongs to one header"
     assert not set(ext._PROTOTYPES_PARTS) & set(ext.EXPORTED_SYMBOLS) and len(ext.EXPORTED_SYMBOLS) == 46

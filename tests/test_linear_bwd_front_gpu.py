@@ -7,6 +7,7 @@ are the statements of its reverse step."""
 import pytest
 import torch
 
+from helpers import count_calls
 from oracle import ttt_oracle as O
 from test_kernels_gpu import DEV, ext, round_acts
 from test_linear_bwd_parts_gpu import GRADS, _case, _grad_bufs, _ranges
@@ -140,20 +141,9 @@ def test_refusals_launch_nothing():
 
 # ------------------------------------------------------------------------------------------------------------- autograd level
 def _count_calls(monkeypatch, e):
-    calls = {"recompute": 0, "sweep": 0, "front": 0, "chain": 0, "one_call": 0}
-    names = {"recompute": "ttt_linear_recompute_groups", "sweep": "ttt_linear_sweep_groups", "front": "ttt_linear_front_groups",
-             "chain": "ttt_linear_chain_groups", "one_call": "ttt_linear_backward_impl"}
-
-    def count(name, fn):
-        def wrapped(*a):
-            calls[name] += 1
-            return fn(*a)
-        return wrapped
-
-    for name, attr in names.items():
-        monkeypatch.setattr(e, attr, count(name, getattr(e, attr)))
-    monkeypatch.setattr(e, "ttt_linear_backward", lambda *a: e.ttt_linear_backward_impl(None, *a))
-    return calls
+    return count_calls(monkeypatch, e, {"recompute": "ttt_linear_recompute_groups", "sweep": "ttt_linear_sweep_groups",
+                                        "front": "ttt_linear_front_groups", "chain": "ttt_linear_chain_groups",
+                                        "one_call": "ttt_linear_backward_impl"})
 
 
 def test_autograd_backward_with_the_front(monkeypatch):

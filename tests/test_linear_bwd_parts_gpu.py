@@ -6,6 +6,7 @@ the step functions of the parts are its steps."""
 import pytest
 import torch
 
+from helpers import count_calls
 from oracle import ttt_oracle as O
 from test_kernels_gpu import DEV, ext, round_acts
 from test_linear_parts_gpu import _layer, _run
@@ -179,20 +180,8 @@ def test_refusals_launch_nothing():
 
 # ------------------------------------------------------------------------------------------------------------- autograd level
 def _count_calls(monkeypatch, e):
-    calls = {"recompute": 0, "sweep": 0, "one_call": 0}
-    orig = e.ttt_linear_recompute_groups, e.ttt_linear_sweep_groups, e.ttt_linear_backward_impl
-
-    def count(name, fn):
-        def wrapped(*a):
-            calls[name] += 1
-            return fn(*a)
-        return wrapped
-
-    monkeypatch.setattr(e, "ttt_linear_recompute_groups", count("recompute", orig[0]))
-    monkeypatch.setattr(e, "ttt_linear_sweep_groups", count("sweep", orig[1]))
-    monkeypatch.setattr(e, "ttt_linear_backward_impl", count("one_call", orig[2]))
-    monkeypatch.setattr(e, "ttt_linear_backward", lambda *a: e.ttt_linear_backward_impl(None, *a))
-    return calls
+    return count_calls(monkeypatch, e, {"recompute": "ttt_linear_recompute_groups", "sweep": "ttt_linear_sweep_groups",
+                                        "one_call": "ttt_linear_backward_impl"})
 
 
 @pytest.mark.parametrize("geometry", GEOMETRIES, ids=["cs16", "cs64"])

@@ -2,13 +2,14 @@
 ``TTT_MLP_CS16_BACKWARD_PARTS`` (ttt_amd/models/ssm/mlp_tk.py), without a device: parsing and validation, the range cutting, and - with
 an extension that only records its calls and stand-ins for the two streams and their events - the schedule of ``backward_in_parts``:
 which entries ``TkMLP.backward`` and ``FusedPreScanMLP.backward`` reach, in which order, on which stream, into which workspace."""
-import contextlib
 import os
 import subprocess
 import sys
 
 import pytest
 import torch
+
+from helpers import fake_streams
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BF16 = torch.bfloat16
@@ -67,17 +68,6 @@ def test_range_cutting_covers_every_group_once_last_range_first():
 
 
 # ------------------------------------------------------------------------------------------------ the recorded schedule
-class FakeStream:
-    def __init__(self, name, log):
-        self.name, self.log = name, log
-
-    def wait_stream(self, other):
-        self.log.append(("wait_stream", self.name, other.name))
-
-    def wait_event(self, ev):
-        self.log.append(("wait_event", self.name, ev.n))
-
-
 class RecordingExt:
     """stands in for ``test_time_training``: every scan entry records its name, the stream it was issued on and its integers"""
 
@@ -140,34 +130,11 @@ class RecordingExt:
 
 @pytest.fixture
 def fake(monkeypatch):
-    from ttt_amd.models.ssm import fused, mlp_tk, pipeline
-    log, current, n_events = [], ["main"], [0]
+    from ttt_amd.models.ssm import fused, mlp_tk
+    log, current = fake_streams(monkeypatch)
     ext = RecordingExt(log, current)
-    main, side = FakeStream("main", log), FakeStream("side", log)
-
-    class FakeEvent:
-        def __init__(self):
-            self.n = n_events[0]
-            n_events[0] += 1
-
-        def record(self, stream):
-            assert stream.name == current[0], "an event is recorded on the stream its work was issued on"
-            log.append(("record", stream.name, self.n))
-
-    @contextlib.contextmanager
-    def on(stream):
-        old, current[0] = current[0], stream.name
-        try:
-            yield
-        finally:
-            current[0] = old
-
     monkeypatch.setattr(mlp_tk, "_ext", lambda: ext)
     monkeypatch.setattr(fused, "_ext", lambda: ext)
-    monkeypatch.setattr(pipeline, "side_stream", lambda device: side)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: main)
-    monkeypatch.setattr(torch.cuda, "Event", FakeEvent)
-    monkeypatch.setattr(torch.cuda, "stream", on)
     return ext
 
 

@@ -412,10 +412,10 @@ def _fill_args(struct, spec, tensors, sizes, act, optional=()):
     return struct(*ptrs)
 
 
-def _scan_args(struct, spec, tensors, checkpoint_group_size, optional=(), impl=None):
+def _scan_args(struct, spec, tensors, checkpoint_group_size, optional=(), impl=None, xq_optional=False):
     """(dims, args, device) of one scan op for ``_launch``: the sizes are XQ's, the tensors are checked against ``spec``; ``impl``
-    overrides the global selector for this call"""
-    XQ = tensors[0]
+    overrides the global selector for this call.  ``xq_optional``: the sizes are XK's where XQ is None (a recompute does not need XQ)"""
+    XQ = tensors[1] if xq_optional and tensors[0] is None else tensors[0]
     _check5(XQ)
     B, NH, NC, CS, F = XQ.shape
     G = int(checkpoint_group_size)
@@ -572,96 +572,81 @@ def ttt_linear_backward_impl(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_no
     _launch("ttt_hip_linear_backward", *_scan_args(_LinBwd, _LIN_BWD_SPEC, tensors, checkpoint_group_size, impl=impl))
 
 
-# The TTT-Linear backward over ranges of checkpoint groups (include/ttt_hip_bwd_parts.h).  The recompute reads XK, XV, last_eta, the
-# LayerNorm parameters and the checkpoints; the sweep reads and writes everything else of ``ttt_linear_backward``'s list.  What a call
-# does not touch may be None; what is given is checked against the contract of ``ttt_linear_backward``, field by field.
+# The backward scans over ranges of checkpoint groups: six entries with one launch path.  A call is the tensor list of the one-call
+# backward (``ttt_linear_backward_impl`` / ``ttt_backward``), then checkpoint_group_size, k0, nk and the raw workspaces of the entry.
+# What an entry does not touch may be None; what is given is checked against the contract of the one-call backward, field by field.
+def _groups_call(symbol, struct, spec, optional, impl, call, workspaces, counter):
+    """``symbol``(dims, args, k0, nk, (pointer, bytes) of each of ``workspaces``, stream) on the current stream; ``counter``: the
+    (dict, key) of this entry's launch count"""
+    n = len(struct._fields_)
+    if len(call) != n + 3 + len(workspaces):
+        raise TypeError(f"{symbol}: expected {n} tensors (or None), checkpoint_group_size, k0, nk, {', '.join(workspaces)}: "
+                        f"{n + 3 + len(workspaces)} arguments, got {len(call)}")
+    (G, k0, nk), raw = call[n:n + 3], call[n + 3:]
+    dims, args, device = _scan_args(struct, spec, call[:n], G, optional, impl, xq_optional=True)
+    lib = load_library()
+    sized = []
+    for name, t in zip(workspaces, raw):          # raw workspaces: any dtype; the library checks the size against the range of the call
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError(f"{name}: expected a contiguous tensor on a HIP device")
+        if name == "ln_carry" and t.dtype != torch.float32:
+            raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {t.dtype}")
+        sized += [_p(t), t.numel() * t.element_size()]
+    with torch.cuda.device(device):
+        rc = getattr(lib, symbol)(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), *sized, torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    counter[0][counter[1]] += 1
+
+
+def _parts_bytes(symbol, B, NH, NC, CS, F, G, act_dtype, impl, *nk):
+    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
+    return int(getattr(load_library(), symbol)(ctypes.byref(d), *(int(v) for v in nk)))
+
+
+# TTT-Linear (include/ttt_hip_bwd_parts.h).  The recompute reads XK, XV, last_eta, the LayerNorm parameters and the checkpoints; the
+# sweep reads and writes everything else of ``ttt_linear_backward``'s list.
 _LIN_RECOMPUTE_FIELDS = frozenset(("XK", "XV", "last_eta", "ttt_norm_weight", "ttt_norm_bias", "W1_checkpoints", "b1_checkpoints"))
 _LIN_SWEEP_UNUSED = frozenset(("W1_checkpoints", "b1_checkpoints", "W1_init_group", "b1_init_group"))
 linear_bwd_parts_calls = {"recompute": 0, "sweep": 0}      # launches of this process (tests, tools)
 
 
-def _lin_bwd_part_args(impl, tensors, checkpoint_group_size, optional):
-    XQ = tensors[0] if tensors[0] is not None else tensors[1]          # (the recompute does not need XQ: XK has its shape)
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
-    args = _fill_args(_LinBwd, _LIN_BWD_SPEC, tensors, sizes, XQ.dtype, optional)
-    return _dims(B, NH, NC, CS, F, G, XQ.dtype, impl), args, XQ.device
-
-
-def _device_bytes(t, name):
-    """a raw workspace: any dtype; the library checks its size against the range of the call"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
-        raise RuntimeError(f"{name}: expected a contiguous tensor on a HIP device")
-
-
 def linear_backward_parts_slots(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
     """bytes of the slot workspace of ``ttt_linear_recompute_groups`` / ``ttt_linear_sweep_groups`` for ``nk`` checkpoint groups:
     B * NH * nk * (G + 1) slots of 16384 + 256 bytes"""
-    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
-    return int(load_library().ttt_hip_linear_backward_parts_slots(ctypes.byref(d), int(nk)))
+    return _parts_bytes("ttt_hip_linear_backward_parts_slots", B, NH, NC, CS, F, G, act_dtype, impl, nk)
 
 
 def linear_backward_parts_carry(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, *, impl=None) -> int:
     """bytes of ``ln_carry``: B * NH * 8 * lanes * 4, lanes = 64 at mini-batches of 16, 256 at mini-batches of 64"""
-    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
-    return int(load_library().ttt_hip_linear_backward_parts_carry(ctypes.byref(d)))
+    return _parts_bytes("ttt_hip_linear_backward_parts_carry", B, NH, NC, CS, F, G, act_dtype, impl)
 
 
-def ttt_linear_recompute_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
-                                grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
-                                grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
-                                grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots):
+def ttt_linear_recompute_groups(impl, *call):
     """Re-run the checkpoint groups [k0, k0 + nk) of the sequence the (whole-sequence) tensors describe from their checkpoints and
     leave the state entering every step, and the state ending each group, in ``slots`` (``linear_backward_parts_slots`` bytes for
-    nk groups) - ``ttt_hip_linear_recompute_groups``, include/ttt_hip_bwd_parts.h.  The tensor list of ``ttt_linear_backward_impl``;
-    only XK, XV, last_eta, the LayerNorm parameters and the checkpoints are needed, the rest may be None.  MFMA sweep only."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
-               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
-               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(LIN_BWD_FIELDS) - _LIN_RECOMPUTE_FIELDS)
-    lib = load_library()
-    _device_bytes(slots, "slots")                 # (its size is the library's check: it knows whether the range is one)
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_linear_recompute_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                                 slots.numel() * slots.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    linear_bwd_parts_calls["recompute"] += 1
+    nk groups) - ``ttt_hip_linear_recompute_groups``, include/ttt_hip_bwd_parts.h.  ``call``: the 21 tensors of
+    ``ttt_linear_backward_impl``, checkpoint_group_size, k0, nk, slots; only XK, XV, last_eta, the LayerNorm parameters and the
+    checkpoints are needed, the rest may be None.  MFMA sweep only."""
+    _groups_call("ttt_hip_linear_recompute_groups", _LinBwd, _LIN_BWD_SPEC, frozenset(LIN_BWD_FIELDS) - _LIN_RECOMPUTE_FIELDS, impl, call,
+                 ("slots",), (linear_bwd_parts_calls, "recompute"))
 
 
-def ttt_linear_sweep_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
-                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
-                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
-                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, ln_carry):
+def ttt_linear_sweep_groups(impl, *call):
     """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` ``ttt_linear_recompute_groups`` left for the
-    same range (``ttt_hip_linear_sweep_groups``).  Carries dW1 / db1 from ``grad_L_W1_last`` / ``grad_L_b1_last`` to ``grad_L_W1_init``
-    / ``grad_L_b1_init`` (which may be the same tensors) and the LayerNorm gradients' partial sums in ``ln_carry``
-    (``linear_backward_parts_carry`` bytes, fp32); the range with k0 == 0 also writes ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from
-    the last range to the first, the results are the bits of ``ttt_linear_backward_impl``.  The checkpoints and ``*_init_group`` may be
-    None.  The caller orders a recompute before the sweep of its slots (same stream, or events)."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
-               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
-               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, _LIN_SWEEP_UNUSED)
-    lib = load_library()
-    _device_bytes(slots, "slots")
-    _device_bytes(ln_carry, "ln_carry")
-    if ln_carry.dtype != torch.float32:
-        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_linear_sweep_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                             slots.numel() * slots.element_size(), _p(ln_carry),
-                                             ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    linear_bwd_parts_calls["sweep"] += 1
+    same range (``ttt_hip_linear_sweep_groups``).  ``call``: the 21 tensors of ``ttt_linear_backward_impl``, checkpoint_group_size, k0,
+    nk, slots, ln_carry.  Carries dW1 / db1 from ``grad_L_W1_last`` / ``grad_L_b1_last`` to ``grad_L_W1_init`` / ``grad_L_b1_init`` (which
+    may be the same tensors) and the LayerNorm gradients' partial sums in ``ln_carry`` (``linear_backward_parts_carry`` bytes, fp32);
+    the range with k0 == 0 also writes ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from the last range to the first, the results
+    are the bits of ``ttt_linear_backward_impl``.  The checkpoints and ``*_init_group`` may be None.  The caller orders a recompute
+    before the sweep of its slots (same stream, or events)."""
+    _groups_call("ttt_hip_linear_sweep_groups", _LinBwd, _LIN_BWD_SPEC, _LIN_SWEEP_UNUSED, impl, call,
+                 ("slots", "ln_carry"), (linear_bwd_parts_calls, "sweep"))
 
 
 # The third stage of the TTT-Linear backward over ranges of checkpoint groups, mini-batches of 16 (include/ttt_hip_lin_bwd_front.h).
 # The front reads the four activation tiles and the LayerNorm parameters and writes grad_L_XQ; the chain is the sweep without XV,
-# grad_L_XQW and grad_L_XQ.  As above: what a call does not touch may be None, what is given is checked field by field.
+# grad_L_XQW and grad_L_XQ.
 _LIN_FRONT_FIELDS = frozenset(("XQ", "XK", "XV", "ttt_norm_weight", "ttt_norm_bias", "grad_L_XQW", "grad_L_XQ"))
 _LIN_CHAIN_UNUSED = _LIN_SWEEP_UNUSED | frozenset(("XV", "grad_L_XQW", "grad_L_XQ"))
 linear_bwd_front_calls = {"front": 0, "chain": 0}      # launches of this process (tests, tools)
@@ -670,159 +655,71 @@ linear_bwd_front_calls = {"front": 0, "chain": 0}      # launches of this proces
 def linear_backward_front_records(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
     """bytes of the record workspace of ``ttt_linear_front_groups`` / ``ttt_linear_chain_groups`` for ``nk`` checkpoint groups:
     B * NH * nk * G records of 19456 bytes ; 0 where CS != 16"""
-    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
-    return int(load_library().ttt_hip_linear_backward_front_records(ctypes.byref(d), int(nk)))
+    return _parts_bytes("ttt_hip_linear_backward_front_records", B, NH, NC, CS, F, G, act_dtype, impl, nk)
 
 
-def ttt_linear_front_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
-                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
-                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
-                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, records):
+def ttt_linear_front_groups(impl, *call):
     """The half of every reverse step of the checkpoint groups [k0, k0 + nk) that does not depend on the carried gradients, all steps
     at once, from the ``slots`` ``ttt_linear_recompute_groups`` left for the same range (``ttt_hip_linear_front_groups``,
     include/ttt_hip_lin_bwd_front.h): writes ``grad_L_XQ`` of those steps and one record per step into ``records``
-    (``linear_backward_front_records`` bytes for nk groups).  The tensor list of ``ttt_linear_backward_impl``; only XQ, XK, XV,
-    grad_L_XQW, the LayerNorm parameters and grad_L_XQ are needed, the rest may be None.  MFMA sweep at mini-batches of 16 only."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
-               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
-               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(LIN_BWD_FIELDS) - _LIN_FRONT_FIELDS)
-    lib = load_library()
-    _device_bytes(slots, "slots")
-    _device_bytes(records, "records")
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_linear_front_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                             slots.numel() * slots.element_size(), _p(records),
-                                             records.numel() * records.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    linear_bwd_front_calls["front"] += 1
+    (``linear_backward_front_records`` bytes for nk groups).  ``call``: the 21 tensors of ``ttt_linear_backward_impl``,
+    checkpoint_group_size, k0, nk, slots, records; only XQ, XK, XV, grad_L_XQW, the LayerNorm parameters and grad_L_XQ are needed, the
+    rest may be None.  MFMA sweep at mini-batches of 16 only."""
+    _groups_call("ttt_hip_linear_front_groups", _LinBwd, _LIN_BWD_SPEC, frozenset(LIN_BWD_FIELDS) - _LIN_FRONT_FIELDS, impl, call,
+                 ("slots", "records"), (linear_bwd_front_calls, "front"))
 
 
-def ttt_linear_chain_groups(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,
-                            grad_L_W1_last, grad_L_b1_last, grad_L_XQW_batch, W1_init_group, b1_init_group,
-                            grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_last_eta,
-                            grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, records, ln_carry):
+def ttt_linear_chain_groups(impl, *call):
     """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` and the ``records`` of the same range
     (``ttt_hip_linear_chain_groups``): ``ttt_linear_sweep_groups`` without the work ``ttt_linear_front_groups`` has done - same carries
-    (dW1 / db1 in place, ``ln_carry``), same bits.  XV, grad_L_XQW, grad_L_XQ, the checkpoints and ``*_init_group`` may be None.  The
-    caller orders recompute -> front -> chain of a range (same stream, or events)."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, grad_L_W1_last, grad_L_b1_last,
-               grad_L_XQW_batch, W1_init_group, b1_init_group, grad_L_ttt_norm_weight, grad_L_ttt_norm_bias, grad_L_W1_init,
-               grad_L_b1_init, grad_L_last_eta, grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _lin_bwd_part_args(impl, tensors, checkpoint_group_size, _LIN_CHAIN_UNUSED)
-    lib = load_library()
-    _device_bytes(slots, "slots")
-    _device_bytes(records, "records")
-    _device_bytes(ln_carry, "ln_carry")
-    if ln_carry.dtype != torch.float32:
-        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_linear_chain_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                             slots.numel() * slots.element_size(), _p(records),
-                                             records.numel() * records.element_size(), _p(ln_carry),
-                                             ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    linear_bwd_front_calls["chain"] += 1
+    (dW1 / db1 in place, ``ln_carry``), same bits.  ``call``: the 21 tensors of ``ttt_linear_backward_impl``, checkpoint_group_size, k0,
+    nk, slots, records, ln_carry; XV, grad_L_XQW, grad_L_XQ, the checkpoints and ``*_init_group`` may be None.  The caller orders
+    recompute -> front -> chain of a range (same stream, or events)."""
+    _groups_call("ttt_hip_linear_chain_groups", _LinBwd, _LIN_BWD_SPEC, _LIN_CHAIN_UNUSED, impl, call,
+                 ("slots", "records", "ln_carry"), (linear_bwd_front_calls, "chain"))
 
 
-# The TTT-MLP backward at mini-batches of 16 over ranges of checkpoint groups (include/ttt_hip_mlp_bwd_parts.h).  The recompute reads
-# XK, XV, last_eta, the LayerNorm parameters and the four checkpoint tensors; the sweep reads and writes everything else of
-# ``ttt_backward``'s list except the sixteen re-materialisation buffers.  What a call does not touch may be None; what is given is
-# checked against the contract of ``ttt_backward``, field by field.
+# TTT-MLP at mini-batches of 16 (include/ttt_hip_mlp_bwd_parts.h).  The recompute reads XK, XV, last_eta, the LayerNorm parameters and
+# the four checkpoint tensors; the sweep reads and writes everything else of ``ttt_backward``'s list except the sixteen
+# re-materialisation buffers.
 _MLP_RECOMPUTE_FIELDS = frozenset(("XK", "XV", "last_eta", "ttt_norm_weight", "ttt_norm_bias", "W1_checkpoints", "b1_checkpoints",
                                    "W2_checkpoints", "b2_checkpoints"))
 _MLP_SWEEP_UNUSED = frozenset(("W1_checkpoints", "b1_checkpoints", "W2_checkpoints", "b2_checkpoints", "XQW")) | _MLP_BWD_SCRATCH
 mlp_bwd_parts_calls = {"recompute": 0, "sweep": 0}      # launches of this process (tests, tools)
 
 
-def _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, optional):
-    XQ = tensors[0] if tensors[0] is not None else tensors[1]          # (the recompute does not need XQ: XK has its shape)
-    _check5(XQ)
-    B, NH, NC, CS, F = XQ.shape
-    G = int(checkpoint_group_size)
-    sizes = dict(B=B, NH=NH, NC=NC, CS=CS, F=F, G=G, K=-(-NC // G), H=4 * F)
-    args = _fill_args(_MlpBwd, _MLP_BWD_SPEC, tensors, sizes, XQ.dtype, optional)
-    return _dims(B, NH, NC, CS, F, G, XQ.dtype, impl), args, XQ.device
-
-
 def mlp_backward_parts_slots(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
     """bytes of the slot workspace of ``ttt_recompute_groups`` / ``ttt_sweep_groups`` for ``nk`` checkpoint groups: B * NH * nk * G
     slots of 132352 bytes (the fp32 W1, b1, W2, b2 entering a step)"""
-    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
-    return int(load_library().ttt_hip_mlp_backward_parts_slots(ctypes.byref(d), int(nk)))
+    return _parts_bytes("ttt_hip_mlp_backward_parts_slots", B, NH, NC, CS, F, G, act_dtype, impl, nk)
 
 
 def mlp_backward_parts_carry(B, NH, NC, CS, F, G, act_dtype=torch.bfloat16, *, impl=None) -> int:
     """bytes of ``ln_carry``: B * NH * 2 * 16 * 64 * 4"""
-    d = _dims(B, NH, NC, CS, F, G, act_dtype, impl)
-    return int(load_library().ttt_hip_mlp_backward_parts_carry(ctypes.byref(d)))
+    return _parts_bytes("ttt_hip_mlp_backward_parts_carry", B, NH, NC, CS, F, G, act_dtype, impl)
 
 
-def ttt_recompute_groups(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
-                         b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
-                         std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
-                         x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
-                         grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
-                         grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
-                         grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, *, impl=None):
+def ttt_recompute_groups(*call, impl=None):
     """Re-run the state updates of the checkpoint groups [k0, k0 + nk) of the sequence the (whole-sequence) tensors describe from their
     checkpoints and leave the fp32 state entering every step in ``slots`` (``mlp_backward_parts_slots`` bytes for nk groups) -
-    ``ttt_hip_mlp_recompute_groups``, include/ttt_hip_mlp_bwd_parts.h.  The tensor list of ``ttt_backward``; only XK, XV, last_eta, the
-    LayerNorm parameters and the four checkpoint tensors are needed, the rest may be None.  bf16, head dim 64, mini-batches of 16;
-    ``impl`` None (the global selector), 'auto' or 'mfma' - the parts exist on the MFMA body alone, 'generic' is refused."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
-               b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
-               std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
-               x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
-               grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
-               grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
-               grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, frozenset(MLP_BWD_FIELDS) - _MLP_RECOMPUTE_FIELDS)
-    lib = load_library()
-    _device_bytes(slots, "slots")                 # (its size is the library's check: it knows whether the range is one)
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_mlp_recompute_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                              slots.numel() * slots.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    mlp_bwd_parts_calls["recompute"] += 1
+    ``ttt_hip_mlp_recompute_groups``, include/ttt_hip_mlp_bwd_parts.h.  ``call``: the 42 tensors of ``ttt_backward``,
+    checkpoint_group_size, k0, nk, slots; only XK, XV, last_eta, the LayerNorm parameters and the four checkpoint tensors are needed,
+    the rest may be None.  bf16, head dim 64, mini-batches of 16; ``impl`` None (the global selector), 'auto' or 'mfma' - the parts
+    exist on the MFMA body alone, 'generic' is refused."""
+    _groups_call("ttt_hip_mlp_recompute_groups", _MlpBwd, _MLP_BWD_SPEC, frozenset(MLP_BWD_FIELDS) - _MLP_RECOMPUTE_FIELDS, impl, call,
+                 ("slots",), (mlp_bwd_parts_calls, "recompute"))
 
 
-def ttt_sweep_groups(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
-                     b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
-                     std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
-                     x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
-                     grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
-                     grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
-                     grad_L_XQ, grad_L_XK, grad_L_XV, checkpoint_group_size, k0, nk, slots, ln_carry, *, impl=None):
+def ttt_sweep_groups(*call, impl=None):
     """The reverse walk over the checkpoint groups k0 + nk - 1 .. k0 from the ``slots`` ``ttt_recompute_groups`` left for the same range
-    (``ttt_hip_mlp_sweep_groups``).  Carries dW1 / db1 / dW2 / db2 from ``grad_L_*_last`` to ``grad_L_*_init`` (which may be the same
-    tensors) and the LayerNorm gradients' un-reduced shares in ``ln_carry`` (``mlp_backward_parts_carry`` bytes, fp32); the range with
-    k0 == 0 also writes ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from the last range to the first, the results are the bits of
+    (``ttt_hip_mlp_sweep_groups``).  ``call``: the 42 tensors of ``ttt_backward``, checkpoint_group_size, k0, nk, slots, ln_carry.
+    Carries dW1 / db1 / dW2 / db2 from ``grad_L_*_last`` to ``grad_L_*_init`` (which may be the same tensors) and the LayerNorm
+    gradients' un-reduced shares in ``ln_carry`` (``mlp_backward_parts_carry`` bytes, fp32); the range with k0 == 0 also writes
+    ``grad_L_ttt_norm_weight`` / ``_bias``.  Walked from the last range to the first, the results are the bits of
     ``ttt_backward_impl('mfma', ...)``.  The checkpoints, XQW_batch and the sixteen ``*_group`` buffers may be None.  The caller orders a
     recompute before the sweep of its slots (same stream, or events)."""
-    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints, W2_checkpoints,
-               b2_checkpoints, XQW_batch, W1_init_group, b1_init_group, W2_init_group, b2_init_group, x_hat_ln_group,
-               std_ln_group, X2_group, Z1_group, Z1_bar_group, X2_bar_group, grad_l_wrt_Z2_group, grad_l_wrt_Z1_group,
-               x_hat_fused_group, grad_x_hat_fused_group, grad_output_fused_group, std_fused_group, grad_L_W1_last,
-               grad_L_b1_last, grad_L_W2_last, grad_L_b2_last, grad_L_XQW_batch, grad_L_ttt_norm_weight,
-               grad_L_ttt_norm_bias, grad_L_W1_init, grad_L_b1_init, grad_L_W2_init, grad_L_b2_init, grad_L_last_eta,
-               grad_L_XQ, grad_L_XK, grad_L_XV)
-    dims, args, device = _mlp_bwd_part_args(impl, tensors, checkpoint_group_size, _MLP_SWEEP_UNUSED)
-    lib = load_library()
-    _device_bytes(slots, "slots")
-    _device_bytes(ln_carry, "ln_carry")
-    if ln_carry.dtype != torch.float32:
-        raise RuntimeError(f"ln_carry: expected dtype torch.float32, got {ln_carry.dtype}")
-    with torch.cuda.device(device):
-        rc = lib.ttt_hip_mlp_sweep_groups(ctypes.byref(dims), ctypes.byref(args), int(k0), int(nk), _p(slots),
-                                          slots.numel() * slots.element_size(), _p(ln_carry),
-                                          ln_carry.numel() * ln_carry.element_size(), torch.cuda.current_stream(device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(lib.ttt_hip_last_error().decode())
-    mlp_bwd_parts_calls["sweep"] += 1
+    _groups_call("ttt_hip_mlp_sweep_groups", _MlpBwd, _MLP_BWD_SPEC, _MLP_SWEEP_UNUSED, impl, call,
+                 ("slots", "ln_carry"), (mlp_bwd_parts_calls, "sweep"))
 
 
 # ------------------------------------------------------------------------------------------------

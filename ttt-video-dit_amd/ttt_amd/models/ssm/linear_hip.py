@@ -44,61 +44,46 @@ def _backward_front_default():
 
 def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     """``ttt_linear_backward`` as ranges of ``gpp`` checkpoint groups, walked from the last range to the first (the entries of
-    include/ttt_hip_bwd_parts.h).  ``tensors``: the 21 of ``ttt_linear_backward`` - the ``*_init_group`` scratch is not used; dW1 / db1 are
-    carried IN PLACE in the output buffers, which start as copies of the upstream gradients of the final state (zeros in
-    ``HipLinear.backward``).  The recompute of the range to be swept next runs on ``pipeline.side_stream`` into one of two slot
-    workspaces while the caller's stream sweeps the current range; events order a sweep behind its recompute and a recompute behind
-    the sweep that last read its workspace; the side stream is joined into the caller's stream before this returns.
+    include/ttt_hip_bwd_parts.h), on the schedule of ``pipeline.run_in_parts``: the recompute of the range to be swept next runs on the
+    side stream into one of two slot workspaces while the caller's stream sweeps the current range.  ``tensors``: the 21 of
+    ``ttt_linear_backward`` - the ``*_init_group`` scratch is not used; dW1 / db1 are carried IN PLACE in the output buffers, which
+    start as copies of the upstream gradients of the final state (zeros in ``HipLinear.backward``).  The workspaces are allocated on
+    the caller's stream and not handed to ``record_stream``: the side stream is joined into the caller's stream before this returns,
+    so nothing allocated on that stream later can run before the side stream's last use of them (``record_stream`` would only defer
+    the allocator's reuse of the blocks).
     ``front`` (mini-batches of 16, include/ttt_hip_lin_bwd_front.h): the side stream also runs, behind the recompute of a range, the
     half of its reverse steps that does not depend on the carried gradients (``ttt_linear_front_groups``, into one of two record
-    workspaces), and the caller's stream walks the range with ``ttt_linear_chain_groups`` instead of the sweep.  Same events: ``ready``
-    is recorded behind the front, ``swept`` guards both workspaces of the range."""
-    from ttt_amd.models.ssm.pipeline import side_stream
+    workspaces), and the caller's stream walks the range with ``ttt_linear_chain_groups`` instead of the sweep."""
+    from ttt_amd.models.ssm.pipeline import part_ranges, run_in_parts
     (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, uW1, ub1, dOut, _, _, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV) = tensors
     B, NH, NC, CS, F = XQ.shape
-    K = math.ceil(NC / G)
     dev = XQ.device
-    ranges = [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]       # (k0, nk), the last range first
-    nbytes = ext.linear_backward_parts_slots(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl)
-    slots = [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
-    if front:
-        rbytes = ext.linear_backward_front_records(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl)
-        records = [torch.empty(rbytes, dtype=torch.uint8, device=dev) for _ in range(2)]
-        front_args = (XQ, XK, XV, None, ln_w, ln_b, None, None, None, None, dOut) + (None,) * 7 + (dQ, None, None)
-        chain_args = (XQ, XK, None, last_eta, ln_w, ln_b, None, None, dW1, db1, None, None, None, d_lnw, d_lnb, dW1, db1, d_eta, None, dK, dV)
-    else:
-        records = []
+    ranges = part_ranges(math.ceil(NC / G), gpp)
+    sets = range(min(2, len(ranges)))
+    space = lambda nbytes: [torch.empty(nbytes, dtype=torch.uint8, device=dev) for _ in sets]
+    slots = space(ext.linear_backward_parts_slots(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl))
     carry = torch.empty(ext.linear_backward_parts_carry(B, NH, NC, CS, F, G, XQ.dtype, impl=impl) // 4, dtype=_F32, device=dev)
     dW1.copy_(uW1); db1.copy_(ub1)
-    main, side = torch.cuda.current_stream(dev), side_stream(dev)
     rec_args = (None, XK, XV, last_eta, ln_w, ln_b, W1c, b1c) + (None,) * 13
-    sweep_args = (XQ, XK, XV, last_eta, ln_w, ln_b, None, None, dW1, db1, dOut, None, None, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
-    ready = [torch.cuda.Event() for _ in ranges]        # recompute of range n is done
-    swept = [torch.cuda.Event() for _ in ranges]        # sweep of range n is done: its workspace may be reused
+    if front:
+        records = space(ext.linear_backward_front_records(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl))
+        front_args = (XQ, XK, XV, None, ln_w, ln_b, None, None, None, None, dOut) + (None,) * 7 + (dQ, None, None)
+        walk_args = (XQ, XK, None, last_eta, ln_w, ln_b, None, None, dW1, db1, None, None, None, d_lnw, d_lnb, dW1, db1, d_eta, None, dK, dV)
+    else:
+        walk_args = (XQ, XK, XV, last_eta, ln_w, ln_b, None, None, dW1, db1, dOut, None, None, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
 
-    def recompute(n):
-        with torch.cuda.stream(side):
-            if n >= 2:
-                side.wait_event(swept[n - 2])
-            ext.ttt_linear_recompute_groups(impl, *rec_args, G, *ranges[n], slots[n & 1])
-            if front:
-                ext.ttt_linear_front_groups(impl, *front_args, G, *ranges[n], slots[n & 1], records[n & 1])
-            ready[n].record(side)
-
-    side.wait_stream(main)                              # the inputs, the checkpoints and the workspaces are the caller's stream's
-    for t in slots + records:
-        t.record_stream(side)
-    recompute(0)
-    for n, (k0, nk) in enumerate(ranges):
-        if n + 1 < len(ranges):
-            recompute(n + 1)
-        main.wait_event(ready[n])
+    def side_work(n, p):
+        ext.ttt_linear_recompute_groups(impl, *rec_args, G, *ranges[n], slots[p])
         if front:
-            ext.ttt_linear_chain_groups(impl, *chain_args, G, k0, nk, slots[n & 1], records[n & 1], carry)
+            ext.ttt_linear_front_groups(impl, *front_args, G, *ranges[n], slots[p], records[p])
+
+    def main_work(n, p):
+        if front:
+            ext.ttt_linear_chain_groups(impl, *walk_args, G, *ranges[n], slots[p], records[p], carry)
         else:
-            ext.ttt_linear_sweep_groups(impl, *sweep_args, G, k0, nk, slots[n & 1], carry)
-        swept[n].record(main)
-    main.wait_stream(side)
+            ext.ttt_linear_sweep_groups(impl, *walk_args, G, *ranges[n], slots[p], carry)
+
+    run_in_parts(dev, ranges, side_work, main_work)
 
 
 class HipLinear(torch.autograd.Function):

@@ -19,6 +19,8 @@ import os
 
 import torch
 
+from ttt_amd.models.ssm.pipeline import part_ranges, run_in_parts  # noqa: F401  (part_ranges: tools and tests import it from here)
+
 _BF16, _F32 = torch.bfloat16, torch.float32
 CS16_BWD_IMPLS = ("auto", "mfma")
 
@@ -49,20 +51,14 @@ def _ext():
     return test_time_training
 
 
-def part_ranges(K, gpp):
-    """(k0, nk) of the K checkpoint groups cut into ranges of ``gpp``, the LAST range first; the first range takes the remainder"""
-    return [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]
-
-
 def backward_in_parts(ext, gpp, tensors, G):
     """``ttt_backward_impl("mfma", ...)`` at mini-batches of 16 as ranges of ``gpp`` checkpoint groups, walked from the last range to
-    the first (the entries of include/ttt_hip_mlp_bwd_parts.h), on the schedule of ``linear_hip.backward_in_parts``.  ``tensors``: the
-    42 of ``ttt_backward`` - the sixteen re-materialisation buffers are not used (None is fine); dW1 .. db2 are carried IN PLACE in
-    the output buffers, which start as copies of the upstream gradients of the final state.  The recompute of the range to be swept
-    next runs on ``pipeline.side_stream`` into one of two slot workspaces while the caller's stream sweeps the current range; events
-    order a sweep behind its recompute and a recompute behind the sweep that last read its workspace; the side stream is joined into
-    the caller's stream before this returns (so the workspaces, allocated on the caller's stream, are not reused before it is done)."""
-    from ttt_amd.models.ssm.pipeline import side_stream
+    the first (the entries of include/ttt_hip_mlp_bwd_parts.h), on the schedule of ``pipeline.run_in_parts``: the recompute of the range
+    to be swept next runs on the side stream into one of two slot workspaces while the caller's stream sweeps the current range.
+    ``tensors``: the 42 of ``ttt_backward`` - the sixteen re-materialisation buffers are not used (None is fine); dW1 .. db2 are
+    carried IN PLACE in the output buffers, which start as copies of the upstream gradients of the final state.  The side stream is
+    joined into the caller's stream before this returns (so the workspaces, allocated on the caller's stream, are not reused before
+    it is done)."""
     XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c = tensors[:10]
     up, dOut, (d_lnw, d_lnb), d_state, (d_eta, dQ, dK, dV) = tensors[27:31], tensors[31], tensors[32:34], tensors[34:38], tensors[38:42]
     B, NH, NC, CS, F = XQ.shape
@@ -73,28 +69,11 @@ def backward_in_parts(ext, gpp, tensors, G):
     carry = torch.empty(ext.mlp_backward_parts_carry(B, NH, NC, CS, F, G, XQ.dtype, impl="mfma") // 4, dtype=_F32, device=dev)
     for d, u in zip(d_state, up):
         d.copy_(u)
-    main, side = torch.cuda.current_stream(dev), side_stream(dev)
     rec_args = (None, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, W2c, b2c) + (None,) * 32
     sweep_args = (XQ, XK, XV, last_eta, ln_w, ln_b) + (None,) * 21 + (*d_state, dOut, d_lnw, d_lnb, *d_state, d_eta, dQ, dK, dV)
-    ready = [torch.cuda.Event() for _ in ranges]        # recompute of range n is done
-    swept = [torch.cuda.Event() for _ in ranges]        # sweep of range n is done: its workspace may be reused
-
-    def recompute(n):
-        with torch.cuda.stream(side):
-            if n >= 2:
-                side.wait_event(swept[n - 2])
-            ext.ttt_recompute_groups(*rec_args, G, *ranges[n], slots[n & 1], impl="mfma")
-            ready[n].record(side)
-
-    side.wait_stream(main)                              # the inputs, the checkpoints and the workspaces are the caller's stream's
-    recompute(0)
-    for n, (k0, nk) in enumerate(ranges):
-        if n + 1 < len(ranges):
-            recompute(n + 1)
-        main.wait_event(ready[n])
-        ext.ttt_sweep_groups(*sweep_args, G, k0, nk, slots[n & 1], carry, impl="mfma")
-        swept[n].record(main)
-    main.wait_stream(side)
+    run_in_parts(dev, ranges,
+                 lambda n, p: ext.ttt_recompute_groups(*rec_args, G, *ranges[n], slots[p], impl="mfma"),
+                 lambda n, p: ext.ttt_sweep_groups(*sweep_args, G, *ranges[n], slots[p], carry, impl="mfma"))
 
 
 def _scan_pair_applies(ext, XQ, G):

@@ -42,6 +42,43 @@ def side_stream(device) -> torch.cuda.Stream:
     return st
 
 
+# ---- the backward scans in parts: ranges of checkpoint groups, the next range prepared beside the walk of the current one ----------
+def part_ranges(K, gpp):
+    """(k0, nk) of the K checkpoint groups cut into ranges of ``gpp``, the LAST range first; the first range takes the remainder"""
+    return [(max(k1 - gpp, 0), k1 - max(k1 - gpp, 0)) for k1 in range(K, 0, -gpp)]
+
+
+def run_in_parts(device, ranges, side_work, main_work):
+    """The schedule of a backward in parts (``linear_hip.backward_in_parts``, ``mlp_tk.backward_in_parts``): streams, events and their
+    order, nothing else.  ``side_work(n, parity)`` issues, on ``side_stream``, everything range n needs before its walk (recompute[,
+    front]) into workspace set ``parity`` = n & 1; ``main_work(n, parity)`` issues the walk of range n on the caller's stream.  The
+    side work of range n + 1 is issued before the walk of range n; a walk waits for the event behind its side work (``ready``), the
+    side work of range n + 2 for the event behind walk n (``swept``), which read the workspace set it writes.  The side stream first
+    waits for the caller's stream - the inputs, the checkpoints and the workspaces are that stream's - and is joined into it before
+    this returns, so that nothing allocated on the caller's stream afterwards can run before the side stream's last use of a
+    workspace: the workspaces, allocated on the caller's stream, need no ``record_stream``."""
+    main, side = torch.cuda.current_stream(device), side_stream(device)
+    ready = [torch.cuda.Event() for _ in ranges]        # the side work of range n is done
+    swept = [torch.cuda.Event() for _ in ranges]        # the walk of range n is done: its workspace set may be reused
+
+    def prepare(n):
+        with torch.cuda.stream(side):
+            if n >= 2:
+                side.wait_event(swept[n - 2])
+            side_work(n, n & 1)
+            ready[n].record(side)
+
+    side.wait_stream(main)
+    prepare(0)
+    for n in range(len(ranges)):
+        if n + 1 < len(ranges):
+            prepare(n + 1)
+        main.wait_event(ready[n])
+        main_work(n, n & 1)
+        swept[n].record(main)
+    main.wait_stream(side)
+
+
 # ---- injection: results of the pre-pass that the autograd Functions take instead of computing -----------------------------------
 class injecting:
     """``with injecting({"linear3": (q, k, v), "scan": (out, *cks), "post": y, "wo": o}): ...`` - every entry must be taken once

@@ -52,13 +52,49 @@ static int post_launch(const char* what) {
 
 #define NEED(p) do { if (!(a->p)) return fail("ttt_hip: null pointer argument %s", #p); } while (0)
 
-// the 15 tensors of the TTT-MLP forward: ttt_hip_mlp_forward and ttt_hip_mlp_forward_chunk
-static int check_mlp_fwd_args(const ttt_mlp_fwd_args* a) {
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+// the six inputs that open the list of nearly every scan entry
+#define NEED_INPUTS() NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias)
+
+// every scan entry begins with these two
+static int check_entry(const ttt_dims* d, const void* a) {
+    if (check_dims(d)) return -1;
+    return a ? 0 : fail("ttt_hip: null args");
+}
+// the 15 tensors of the TTT-MLP forward: ttt_hip_mlp_forward, ttt_hip_mlp_forward_chunk and ttt_hip_mlp_forward_chunk_pair16
+static int check_mlp_fwd_args(const ttt_dims* d, const ttt_mlp_fwd_args* a) {
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
     NEED(W1_init); NEED(b1_init); NEED(W2_init); NEED(b2_init);
     NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints); NEED(XQW);
     return 0;
+}
+// the 11 tensors of the TTT-Linear forward: ttt_hip_linear_forward and ttt_hip_linear_forward_chunk
+static int check_linear_fwd_args(const ttt_dims* d, const ttt_linear_fwd_args* a) {
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
+    NEED(W1_init); NEED(b1_init); NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(XQW);
+    return 0;
+}
+
+// Checks that several scan entries share.  `what`: the entry's name in its messages.
+static int check_steps(const char* what, const ttt_dims* d, int step0, int nsteps) {
+    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps) return fail("ttt_hip: %s: the part [step0, step0 + nsteps) must lie inside [0, NC)", what);
+    return 0;
+}
+static int check_finals4(const char* what, const float* W1f, const float* b1f, const float* W2f, const float* b2f) {
+    if ((W1f || b1f || W2f || b2f) && !(W1f && b1f && W2f && b2f)) return fail("ttt_hip: %s: give all four final-state buffers or none", what);
+    return 0;
+}
+static int check_groups(const char* what, const ttt_dims* d, int k0, int nk) {
+    const int K = (d->NC + d->G - 1) / d->G;
+    if (k0 < 0 || nk <= 0 || k0 > K - nk) return fail("ttt_hip: %s: the groups [k0, k0 + nk) must lie inside [0, K)", what);
+    return 0;
+}
+// the carry of a sweep / chain, `need` bytes; the TTT-MLP sweep's (`aligned`) is read 16 bytes at a time
+static int check_carry(const char* what, const float* ln_carry, size_t carry_bytes, size_t need, bool aligned) {
+    if (ln_carry && carry_bytes >= need && !(aligned && ((uintptr_t)ln_carry & 15))) return 0;
+    return fail(aligned ? "ttt_hip: %s: ln_carry null, not 16-byte aligned or smaller than ttt_hip_mlp_backward_parts_carry(d)"
+                        : "ttt_hip: %s: ln_carry null or smaller than ttt_hip_linear_backward_parts_carry(d)", what);
 }
 
 // a strided ttt_attn_tensor `t` into the flat fields of an attention parameter block: pointer p.PTR, strides p.PRE_sb / _sh / _ss
@@ -163,11 +199,19 @@ size_t ttt_hip_mlp_backward_workspace(const ttt_dims* d) { return ws_bytes(d, tr
 size_t ttt_hip_linear_forward_workspace(const ttt_dims* d) { return ws_bytes(d, false, false); }
 size_t ttt_hip_linear_backward_workspace(const ttt_dims* d) { return ws_bytes(d, false, true); }
 
+// the four one-call entries: the implementation that serves `d`, once the caller's workspace is seen to hold what it asks for
+static int resolve_with_ws(const char* what, const ttt_dims* d, bool mlp, bool bwd, const void* ws, size_t wsb) {
+    const int r = resolve(d, mlp, bwd);
+    if (r < 0) return fail("ttt_hip: %s: unsupported geometry/dtype for the requested impl", what);
+    const size_t need = ws_bytes(d, mlp, bwd);
+    if (wsb < need || (need && !ws)) return fail("ttt_hip: %s: workspace too small", what);
+    return r;
+}
+
 int ttt_hip_mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
-    int r = resolve(d, true, false);
-    if (r < 0) return fail("ttt_hip: mlp_forward: unsupported geometry/dtype for the requested impl");
-    if (wsb < ws_bytes(d, true, false) || (ws_bytes(d, true, false) && !ws)) return fail("ttt_hip: mlp_forward: workspace too small");
+    if (check_mlp_fwd_args(d, a)) return -1;
+    const int r = resolve_with_ws("mlp_forward", d, true, false, ws, wsb);
+    if (r < 0) return -1;
     if (check_sweep_error("mlp_forward")) return -3;
     if (r == TTT_IMPL_MFMA) ttt::mfma::mlp_forward(d, a, ws, (hipStream_t)stream);
     else ttt::generic::mlp_forward(d, a, ws, (hipStream_t)stream);
@@ -176,16 +220,14 @@ int ttt_hip_mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, 
 
 int ttt_hip_mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                               float* W2_final, float* b2_final, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
+    if (check_mlp_fwd_args(d, a)) return -1;
     if (resolve(d, true, false) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
         return fail("ttt_hip: mlp_forward_chunk: only the MFMA scan (mini-batches of 64 or 16) continues from a state");
-    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
-        return fail("ttt_hip: mlp_forward_chunk: the part [step0, step0 + nsteps) must lie inside [0, NC)");
+    if (check_steps("mlp_forward_chunk", d, step0, nsteps)) return -1;
     // CS = 64 hands over at checkpoint-group boundaries; the CS = 16 scan (one group in sampling) continues from any step
     if (d->CS == 64 && (step0 % d->G != 0 || ((step0 + nsteps) % d->G != 0 && step0 + nsteps != d->NC)))
         return fail("ttt_hip: mlp_forward_chunk: a part of the sequence starts and ends at checkpoint-group boundaries (or at the end)");
-    if ((W1_final || b1_final || W2_final || b2_final) && !(W1_final && b1_final && W2_final && b2_final))
-        return fail("ttt_hip: mlp_forward_chunk: give all four final-state buffers or none");
+    if (check_finals4("mlp_forward_chunk", W1_final, b1_final, W2_final, b2_final)) return -1;
     if (check_sweep_error("mlp_forward_chunk")) return -3;
     // the workspace of ttt_hip_mlp_forward_workspace (the pair scan's ring); null / too small: the one-workgroup scan (ABI 4 callers)
     void* use_ws = (ws && wsb >= ws_bytes(d, true, false)) ? ws : nullptr;
@@ -203,13 +245,11 @@ size_t ttt_hip_mlp_forward_pair16_workspace(const ttt_dims* d) {
 }
 int ttt_hip_mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                                      float* W2_final, float* b2_final, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d) || check_mlp_fwd_args(a)) return -1;
+    if (check_mlp_fwd_args(d, a)) return -1;
     if (!pair16_serves(d))
         return fail("ttt_hip: mlp_forward_chunk_pair16: the pair scan serves bf16 activations, F = 64, mini-batches of 16 on the MFMA scan only");
-    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
-        return fail("ttt_hip: mlp_forward_chunk_pair16: the part [step0, step0 + nsteps) must lie inside [0, NC)");
-    if ((W1_final || b1_final || W2_final || b2_final) && !(W1_final && b1_final && W2_final && b2_final))
-        return fail("ttt_hip: mlp_forward_chunk_pair16: give all four final-state buffers or none");
+    if (check_steps("mlp_forward_chunk_pair16", d, step0, nsteps)) return -1;
+    if (check_finals4("mlp_forward_chunk_pair16", W1_final, b1_final, W2_final, b2_final)) return -1;
     if (!ws || wsb < ttt::mfma::scan_pair16_workspace_bytes(d->B * d->NH))
         return fail("ttt_hip: mlp_forward_chunk_pair16: workspace null or smaller than ttt_hip_mlp_forward_pair16_workspace(d)");
     if (check_sweep_error("mlp_forward_chunk_pair16")) return -3;
@@ -220,16 +260,14 @@ int ttt_hip_mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* 
 }
 
 int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
     NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints);
     NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_W2_last); NEED(grad_L_b2_last); NEED(grad_L_XQW);
     NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias); NEED(grad_L_W1_init); NEED(grad_L_b1_init);
     NEED(grad_L_W2_init); NEED(grad_L_b2_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
-    int r = resolve(d, true, true);
-    if (r < 0) return fail("ttt_hip: mlp_backward: unsupported geometry/dtype for the requested impl");
-    if (wsb < ws_bytes(d, true, true) || (ws_bytes(d, true, true) && !ws)) return fail("ttt_hip: mlp_backward: workspace too small");
+    const int r = resolve_with_ws("mlp_backward", d, true, true, ws, wsb);
+    if (r < 0) return -1;
     if (check_sweep_error("mlp_backward")) return -3;
     // the caller-allocated re-materialisation scratch of the reference contract: the generic kernels and the MFMA backward at
     // mini-batches of 16 keep their per-step state in the four *_init_group buffers; the MFMA backward at 64 works in `ws` and
@@ -245,13 +283,9 @@ int ttt_hip_mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws,
 }
 
 int ttt_hip_linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
-    NEED(W1_init); NEED(b1_init); NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(XQW);
-    int r = resolve(d, false, false);
-    if (r < 0) return fail("ttt_hip: linear_forward: unsupported geometry/dtype for the requested impl");
-    if (wsb < ws_bytes(d, false, false) || (ws_bytes(d, false, false) && !ws)) return fail("ttt_hip: linear_forward: workspace too small");
+    if (check_linear_fwd_args(d, a)) return -1;
+    const int r = resolve_with_ws("linear_forward", d, false, false, ws, wsb);
+    if (r < 0) return -1;
     if (r == TTT_IMPL_MFMA) ttt::mfma::linear_forward(d, a, ws, (hipStream_t)stream);
     else ttt::generic::linear_forward(d, a, ws, (hipStream_t)stream);
     return post_launch("linear_forward");
@@ -260,30 +294,24 @@ int ttt_hip_linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void
 // include/ttt_hip_parts.h
 int ttt_hip_linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1_final, float* b1_final,
                                  void*, size_t, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
-    NEED(W1_init); NEED(b1_init); NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(XQW);
+    if (check_linear_fwd_args(d, a)) return -1;
     // (fp32 activations, TTT_IMPL_GENERIC and mini-batches of 64 under TTT_IMPL_AUTO resolve to the generic kernels)
     if (resolve(d, false, false) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
         return fail("ttt_hip: linear_forward_chunk: only the MFMA scan (mini-batches of 16; of 64 on an explicit TTT_IMPL_MFMA) continues from a state");
-    if (step0 < 0 || nsteps <= 0 || step0 > d->NC - nsteps)
-        return fail("ttt_hip: linear_forward_chunk: the part [step0, step0 + nsteps) must lie inside [0, NC)");
+    if (check_steps("linear_forward_chunk", d, step0, nsteps)) return -1;
     if (!W1_final != !b1_final) return fail("ttt_hip: linear_forward_chunk: give both final-state buffers or neither");
     ttt::mfma::linear_forward_chunk(d, a, step0, nsteps, W1_final, b1_final, (hipStream_t)stream);
     return post_launch("linear_forward_chunk");
 }
 
 int ttt_hip_linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* ws, size_t wsb, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
     NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_XQW);
     NEED(W1_init_group); NEED(b1_init_group); NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias);
     NEED(grad_L_W1_init); NEED(grad_L_b1_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
-    int r = resolve(d, false, true);
-    if (r < 0) return fail("ttt_hip: linear_backward: unsupported geometry/dtype for the requested impl");
-    if (wsb < ws_bytes(d, false, true) || (ws_bytes(d, false, true) && !ws)) return fail("ttt_hip: linear_backward: workspace too small");
+    const int r = resolve_with_ws("linear_backward", d, false, true, ws, wsb);
+    if (r < 0) return -1;
     if (r == TTT_IMPL_MFMA) ttt::mfma::linear_backward(d, a, ws, (hipStream_t)stream);
     else ttt::generic::linear_backward(d, a, ws, (hipStream_t)stream);
     return post_launch("linear_backward");
@@ -294,8 +322,7 @@ static int check_bwd_parts(const char* fmt_what, const ttt_dims* d, int k0, int 
     // (fp32 activations, TTT_IMPL_GENERIC and mini-batches of 64 under TTT_IMPL_AUTO resolve to the generic kernels)
     if (resolve(d, false, true) != TTT_IMPL_MFMA || (d->CS != 64 && d->CS != 16))
         return fail("ttt_hip: %s: only the MFMA sweep (mini-batches of 16; of 64 on an explicit TTT_IMPL_MFMA) runs over a range of checkpoint groups", fmt_what);
-    const int K = (d->NC + d->G - 1) / d->G;
-    if (k0 < 0 || nk <= 0 || k0 > K - nk) return fail("ttt_hip: %s: the groups [k0, k0 + nk) must lie inside [0, K)", fmt_what);
+    if (check_groups(fmt_what, d, k0, nk)) return -1;
     if (!slots || slots_bytes < ttt::mfma::linear_backward_parts_slots(d, nk))
         return fail("ttt_hip: %s: slot workspace null or smaller than ttt_hip_linear_backward_parts_slots(d, nk)", fmt_what);
     return 0;
@@ -310,8 +337,7 @@ size_t ttt_hip_linear_backward_parts_carry(const ttt_dims* d) {
 }
 int ttt_hip_linear_recompute_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, void* slots, size_t slots_bytes,
                                     void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
+    if (check_entry(d, a)) return -1;
     NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias); NEED(W1_checkpoints); NEED(b1_checkpoints);
     if (check_bwd_parts("linear_recompute_groups", d, k0, nk, slots, slots_bytes)) return -1;
     ttt::mfma::linear_recompute_groups(d, a, k0, nk, slots, (hipStream_t)stream);
@@ -319,14 +345,12 @@ int ttt_hip_linear_recompute_groups(const ttt_dims* d, const ttt_linear_bwd_args
 }
 int ttt_hip_linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
                                 float* ln_carry, size_t carry_bytes, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
     NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_XQW); NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias);
     NEED(grad_L_W1_init); NEED(grad_L_b1_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
     if (check_bwd_parts("linear_sweep_groups", d, k0, nk, slots, slots_bytes)) return -1;
-    if (!ln_carry || carry_bytes < ttt::mfma::linear_backward_parts_carry(d))
-        return fail("ttt_hip: linear_sweep_groups: ln_carry null or smaller than ttt_hip_linear_backward_parts_carry(d)");
+    if (check_carry("linear_sweep_groups", ln_carry, carry_bytes, ttt::mfma::linear_backward_parts_carry(d), false)) return -1;
     ttt::mfma::linear_sweep_groups(d, a, k0, nk, slots, ln_carry, (hipStream_t)stream);
     return post_launch("linear_sweep_groups");
 }
@@ -347,8 +371,7 @@ size_t ttt_hip_linear_backward_front_records(const ttt_dims* d, int nk) {
 }
 int ttt_hip_linear_front_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
                                 void* records, size_t records_bytes, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
+    if (check_entry(d, a)) return -1;
     NEED(XQ); NEED(XK); NEED(XV); NEED(ttt_norm_weight); NEED(ttt_norm_bias); NEED(grad_L_XQW); NEED(grad_L_XQ);
     if (check_bwd_front("linear_front_groups", d, k0, nk, slots, slots_bytes, records, records_bytes)) return -1;
     ttt::mfma::linear_front_groups(d, a, k0, nk, slots, records, (hipStream_t)stream);
@@ -356,14 +379,12 @@ int ttt_hip_linear_front_groups(const ttt_dims* d, const ttt_linear_bwd_args* a,
 }
 int ttt_hip_linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
                                 const void* records, size_t records_bytes, float* ln_carry, size_t carry_bytes, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
+    if (check_entry(d, a)) return -1;
     NEED(XQ); NEED(XK); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
     NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias);
     NEED(grad_L_W1_init); NEED(grad_L_b1_init); NEED(grad_L_last_eta); NEED(grad_L_XK); NEED(grad_L_XV);
     if (check_bwd_front("linear_chain_groups", d, k0, nk, slots, slots_bytes, records, records_bytes)) return -1;
-    if (!ln_carry || carry_bytes < ttt::mfma::linear_backward_parts_carry(d))
-        return fail("ttt_hip: linear_chain_groups: ln_carry null or smaller than ttt_hip_linear_backward_parts_carry(d)");
+    if (check_carry("linear_chain_groups", ln_carry, carry_bytes, ttt::mfma::linear_backward_parts_carry(d), false)) return -1;
     ttt::mfma::linear_chain_groups(d, a, k0, nk, slots, records, ln_carry, (hipStream_t)stream);
     return post_launch("linear_chain_groups");
 }
@@ -377,8 +398,7 @@ static bool mlp_bwd_parts_serves(const ttt_dims* d) {
 static int check_mlp_bwd_parts(const char* fmt_what, const ttt_dims* d, int k0, int nk, const void* slots, size_t slots_bytes) {
     if (!mlp_bwd_parts_serves(d))
         return fail("ttt_hip: %s: only the MFMA backward at mini-batches of 16 (bf16 activations, F = 64, TTT_IMPL_MFMA or TTT_IMPL_AUTO) runs over a range of checkpoint groups", fmt_what);
-    const int K = (d->NC + d->G - 1) / d->G;
-    if (k0 < 0 || nk <= 0 || k0 > K - nk) return fail("ttt_hip: %s: the groups [k0, k0 + nk) must lie inside [0, K)", fmt_what);
+    if (check_groups(fmt_what, d, k0, nk)) return -1;
     if (!slots || slots_bytes < ttt::mfma::mlp_backward_parts_slots(d, nk))
         return fail("ttt_hip: %s: slot workspace null or smaller than ttt_hip_mlp_backward_parts_slots(d, nk)", fmt_what);
     if ((uintptr_t)slots & 15) return fail("ttt_hip: %s: the slot workspace must be 16-byte aligned", fmt_what);
@@ -393,8 +413,7 @@ size_t ttt_hip_mlp_backward_parts_carry(const ttt_dims* d) {
     return ttt::mfma::mlp_backward_parts_carry(d);
 }
 int ttt_hip_mlp_recompute_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, void* slots, size_t slots_bytes, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
+    if (check_entry(d, a)) return -1;
     NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
     NEED(W1_checkpoints); NEED(b1_checkpoints); NEED(W2_checkpoints); NEED(b2_checkpoints);
     if (check_mlp_bwd_parts("mlp_recompute_groups", d, k0, nk, slots, slots_bytes)) return -1;
@@ -403,15 +422,13 @@ int ttt_hip_mlp_recompute_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, i
 }
 int ttt_hip_mlp_sweep_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
                              float* ln_carry, size_t carry_bytes, void* stream) {
-    if (check_dims(d)) return -1;
-    if (!a) return fail("ttt_hip: null args");
-    NEED(XQ); NEED(XK); NEED(XV); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    if (check_entry(d, a)) return -1;
+    NEED_INPUTS();
     NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_W2_last); NEED(grad_L_b2_last); NEED(grad_L_XQW);
     NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias); NEED(grad_L_W1_init); NEED(grad_L_b1_init);
     NEED(grad_L_W2_init); NEED(grad_L_b2_init); NEED(grad_L_last_eta); NEED(grad_L_XQ); NEED(grad_L_XK); NEED(grad_L_XV);
     if (check_mlp_bwd_parts("mlp_sweep_groups", d, k0, nk, slots, slots_bytes)) return -1;
-    if (!ln_carry || carry_bytes < ttt::mfma::mlp_backward_parts_carry(d) || ((uintptr_t)ln_carry & 15))
-        return fail("ttt_hip: mlp_sweep_groups: ln_carry null, not 16-byte aligned or smaller than ttt_hip_mlp_backward_parts_carry(d)");
+    if (check_carry("mlp_sweep_groups", ln_carry, carry_bytes, ttt::mfma::mlp_backward_parts_carry(d), true)) return -1;
     ttt::mfma::mlp_sweep_groups(d, a, k0, nk, slots, ln_carry, (hipStream_t)stream);
     return post_launch("mlp_sweep_groups");
 }

@@ -21,4 +21,12 @@ struct OncePerDevice {
         }
     }
 };
+
+// launch `Kernel` with `lds` bytes of dynamic LDS; its dynamic-LDS limit is raised to `lds` once per device, under the lock
+template <auto Kernel, class... A>
+void launch_lds(int grid, int threads, int lds, hipStream_t s, const A&... args) {
+    static OncePerDevice done;
+    done.run([&] { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, args...);
+}
 }  // namespace ttt

@@ -26,16 +26,24 @@ bool supports(const ttt_dims* d, bool mlp, bool backward) {
     return d->CS == 64 && (!backward || bwd_available());
 }
 
-void mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, hipStream_t s) {
+static int n_bh(const ttt_dims* d) { return d->B * d->NH; }
+static int n_groups(const ttt_dims* d) { return (d->NC + d->G - 1) / d->G; }
+
+// the fifteen tensors and the geometry of the whole sequence, NCs = 0 ("one call", no final-state store): a part sets NC, NCs, ck0, W1f .. b2f
+static ScanParams scan_params(const ttt_dims* d, const ttt_mlp_fwd_args* a) {
     ScanParams p = {};
     p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
     p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
     p.W1 = a->W1_init; p.b1 = a->b1_init; p.W2 = a->W2_init; p.b2 = a->b2_init;
     p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints; p.W2c = a->W2_checkpoints; p.b2c = a->b2_checkpoints;
     p.out = (__bf16*)a->XQW;
-    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    if (d->CS == 16) launch_scan_forward_cs16(p, d->B * d->NH, g_dbg, s);
-    else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
+    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = n_groups(d); p.eps = d->eps;
+    return p;
+}
+void mlp_forward(const ttt_dims* d, const ttt_mlp_fwd_args* a, void* ws, hipStream_t s) {
+    const ScanParams p = scan_params(d, a);
+    if (d->CS == 16) launch_scan_forward_cs16(p, n_bh(d), g_dbg, s);
+    else launch_scan_forward_v2(p, n_bh(d), ws, g_dbg, s);
 }
 // TTT-MLP backward at CS = 16: the per-step state lives in the caller's four *_init_group buffers, nothing in `ws`
 static wv::Mlp16BwdParams mlp16_bwd_params(const ttt_dims* d, const ttt_mlp_bwd_args* a) {
@@ -49,11 +57,11 @@ static wv::Mlp16BwdParams mlp16_bwd_params(const ttt_dims* d, const ttt_mlp_bwd_
     p.dln_w = a->grad_L_ttt_norm_weight; p.dln_b = a->grad_L_ttt_norm_bias;
     p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init; p.dW2 = a->grad_L_W2_init; p.db2 = a->grad_L_b2_init;
     p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
-    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = n_groups(d); p.eps = d->eps;
     return p;
 }
 void mlp_backward_cs16(const ttt_dims* d, const ttt_mlp_bwd_args* a, hipStream_t s) {
-    launch_mlp_backward_cs16(mlp16_bwd_params(d, a), d->B * d->NH, s);
+    launch_mlp_backward_cs16(mlp16_bwd_params(d, a), n_bh(d), s);
 }
 // The same backward in parts (ttt_wave_types.h: Mlp16BwdPartParams).  G slots per group: the fp32 state entering each step ; the
 // carry: the 2 x 16 x 64 cells of the owners' dln shares per (b, h).
@@ -63,11 +71,11 @@ size_t mlp_backward_parts_slots(const ttt_dims* d, int nk) {
 size_t mlp_backward_parts_carry(const ttt_dims* d) { return (size_t)d->B * d->NH * wv::MLP16_PART_CARRY_FLOATS * sizeof(float); }
 void mlp_recompute_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, void* slots, hipStream_t s) {
     const wv::Mlp16BwdPartParams q = {mlp16_bwd_params(d, a), k0, nk, (float*)slots, nullptr};
-    launch_mlp_recompute_groups(q, d->B * d->NH, s);
+    launch_mlp_recompute_groups(q, n_bh(d), s);
 }
 void mlp_sweep_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int nk, const void* slots, float* ln_carry, hipStream_t s) {
     const wv::Mlp16BwdPartParams q = {mlp16_bwd_params(d, a), k0, nk, (float*)const_cast<void*>(slots), ln_carry};
-    launch_mlp_sweep_groups(q, d->B * d->NH, s);
+    launch_mlp_sweep_groups(q, n_bh(d), s);
 }
 // steps [step0, step0 + nsteps) of the scan: the same kernel over a part of the sequence, started from the state in
 // a->*_init (what the previous part left in *_final), its checkpoints written at their places in the whole sequence's arrays.
@@ -75,49 +83,45 @@ void mlp_sweep_groups(const ttt_dims* d, const ttt_mlp_bwd_args* a, int k0, int 
 // step; the body (ttt_mlp16_body.h) takes the whole sequence's pointers and the first step.
 void mlp_forward_chunk(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, float* W2f, float* b2f,
                        void* ws, hipStream_t s) {
-    ScanParams p = {};
-    const bool cs16 = d->CS == 16;
-    const size_t t0 = cs16 ? 0 : (size_t)step0 * 64 * 64, e0 = cs16 ? 0 : (size_t)step0 * 64;
-    p.XQ = (const __bf16*)a->XQ + t0; p.XK = (const __bf16*)a->XK + t0; p.XV = (const __bf16*)a->XV + t0; p.eta = (const __bf16*)a->last_eta + e0;
-    p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
-    p.W1 = a->W1_init; p.b1 = a->b1_init; p.W2 = a->W2_init; p.b2 = a->b2_init;
-    p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints; p.W2c = a->W2_checkpoints; p.b2c = a->b2_checkpoints;
-    p.out = (__bf16*)a->XQW + t0;
-    p.NH = d->NH; p.NC = nsteps; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    p.NCs = d->NC; p.ck0 = cs16 ? step0 : step0 / d->G;
+    ScanParams p = scan_params(d, a);
+    p.NC = nsteps; p.NCs = d->NC;
     p.W1f = W1f; p.b1f = b1f; p.W2f = W2f; p.b2f = b2f;
-    if (cs16) launch_scan_forward_cs16(p, d->B * d->NH, g_dbg, s);
-    else launch_scan_forward_v2(p, d->B * d->NH, ws, g_dbg, s);
+    if (d->CS == 16) {
+        p.ck0 = step0;
+        launch_scan_forward_cs16(p, n_bh(d), g_dbg, s);
+    } else {
+        const size_t t0 = (size_t)step0 * 64 * 64, e0 = (size_t)step0 * 64;
+        p.XQ += t0; p.XK += t0; p.XV += t0; p.eta += e0; p.out += t0;
+        p.ck0 = step0 / d->G;
+        launch_scan_forward_v2(p, n_bh(d), ws, g_dbg, s);
+    }
 }
 // the same part at CS = 16 as a pair of workgroups per (b, h) (ttt_mlp16_pair_body.h); `ws`: scan_pair16_workspace_bytes
 int mlp_forward_chunk_pair16(const ttt_dims* d, const ttt_mlp_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, float* W2f,
                              float* b2f, void* ws, hipStream_t s) {
-    ScanParams p = {};
-    p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
-    p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
-    p.W1 = a->W1_init; p.b1 = a->b1_init; p.W2 = a->W2_init; p.b2 = a->b2_init;
-    p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints; p.W2c = a->W2_checkpoints; p.b2c = a->b2_checkpoints;
-    p.out = (__bf16*)a->XQW;
-    p.NH = d->NH; p.NC = nsteps; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    p.NCs = d->NC; p.ck0 = step0;
+    ScanParams p = scan_params(d, a);
+    p.NC = nsteps; p.NCs = d->NC; p.ck0 = step0;
     p.W1f = W1f; p.b1f = b1f; p.W2f = W2f; p.b2f = b2f;
-    return launch_scan_forward_pair16(p, d->B * d->NH, ws, s);
+    return launch_scan_forward_pair16(p, n_bh(d), ws, s);
 }
 // steps [step0, step0 + nsteps) of the TTT-Linear scan: the same kernel over a part of the sequence, started from the state in
 // a->W1_init / b1_init, its checkpoints written at their places in the whole sequence's arrays, the state after its last step
 // left in W1f / b1f (both null: not stored).  Parts start at any step at both mini-batch sizes (ttt_wave_types.h).
-void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, hipStream_t s) {
-    wv::Lin16ChunkParams c = {};
-    wv::Lin16Params& p = c.p;
+static wv::Lin16Params lin16_fwd_params(const ttt_dims* d, const ttt_linear_fwd_args* a) {
+    wv::Lin16Params p = {};
     p.XQ = (const __bf16*)a->XQ; p.XK = (const __bf16*)a->XK; p.XV = (const __bf16*)a->XV; p.eta = (const __bf16*)a->last_eta;
     p.ln_w = a->ttt_norm_weight; p.ln_b = a->ttt_norm_bias;
     p.W1 = a->W1_init; p.b1 = a->b1_init;
     p.W1c = a->W1_checkpoints; p.b1c = a->b1_checkpoints;
     p.out = (__bf16*)a->XQW;
-    p.NH = d->NH; p.NC = nsteps; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
-    c.step0 = step0; c.NCs = d->NC; c.W1f = W1f; c.b1f = b1f;
-    if (d->CS == 16) launch_linear_forward_cs16(c, d->B * d->NH, s);
-    else launch_linear_forward_cs64(c, d->B * d->NH, s);
+    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = n_groups(d); p.eps = d->eps;
+    return p;
+}
+void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f, hipStream_t s) {
+    wv::Lin16ChunkParams c = {lin16_fwd_params(d, a), step0, d->NC, W1f, b1f};
+    c.p.NC = nsteps;
+    if (d->CS == 16) launch_linear_forward_cs16(c, n_bh(d), s);
+    else launch_linear_forward_cs64(c, n_bh(d), s);
 }
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipStream_t s) {
     linear_forward_chunk(d, a, 0, d->NC, nullptr, nullptr, s);
@@ -133,13 +137,13 @@ static wv::Lin16Params linear_bwd_params(const ttt_dims* d, const ttt_linear_bwd
     p.dln_w = a->grad_L_ttt_norm_weight; p.dln_b = a->grad_L_ttt_norm_bias;
     p.dW1 = a->grad_L_W1_init; p.db1 = a->grad_L_b1_init;
     p.deta = (__bf16*)a->grad_L_last_eta; p.dXQ = (__bf16*)a->grad_L_XQ; p.dXK = (__bf16*)a->grad_L_XK; p.dXV = (__bf16*)a->grad_L_XV;
-    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = (d->NC + d->G - 1) / d->G; p.eps = d->eps;
+    p.NH = d->NH; p.NC = d->NC; p.G = d->G; p.K = n_groups(d); p.eps = d->eps;
     return p;
 }
 void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void*, hipStream_t s) {
     const wv::Lin16Params p = linear_bwd_params(d, a);
-    if (d->CS == 16) launch_linear_backward_cs16(p, d->B * d->NH, s);
-    else launch_linear_backward_cs64(p, d->B * d->NH, s);
+    if (d->CS == 16) launch_linear_backward_cs16(p, n_bh(d), s);
+    else launch_linear_backward_cs64(p, n_bh(d), s);
 }
 // The backward in parts (ttt_wave_types.h: Lin16BwdPartParams).  G + 1 slots per group: the state entering each step and the state
 // that ends the group ; the carry: 8 partial sums per lane of the scan's wave (CS = 16) or four waves (CS = 64).
@@ -151,11 +155,11 @@ size_t linear_backward_parts_carry(const ttt_dims* d) {
 }
 void linear_recompute_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, void* slots, hipStream_t s) {
     const wv::Lin16BwdPartParams q = {linear_bwd_params(d, a), k0, nk, (char*)slots, nullptr};
-    launch_linear_recompute_groups(q, d->CS, d->B * d->NH, s);
+    launch_linear_recompute_groups(q, d->CS, n_bh(d), s);
 }
 void linear_sweep_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, float* ln_carry, hipStream_t s) {
     const wv::Lin16BwdPartParams q = {linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry};
-    launch_linear_sweep_groups(q, d->CS, d->B * d->NH, s);
+    launch_linear_sweep_groups(q, d->CS, n_bh(d), s);
 }
 // The third stage at mini-batches of 16 (ttt_wave_types.h: Lin16BwdFrontParams): one record per step of the range.
 size_t linear_backward_front_records(const ttt_dims* d, int nk) {
@@ -164,13 +168,13 @@ size_t linear_backward_front_records(const ttt_dims* d, int nk) {
 void linear_front_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, void* records, hipStream_t s) {
     const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), nullptr}, (char*)records};
     const int s_hi = (k0 + nk) * d->G < d->NC ? (k0 + nk) * d->G : d->NC;
-    launch_linear_front_groups(f, d->B * d->NH * (s_hi - k0 * d->G), s);
+    launch_linear_front_groups(f, n_bh(d) * (s_hi - k0 * d->G), s);
 }
 void linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, const void* records,
                          float* ln_carry, hipStream_t s) {
     const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry},
                                        (char*)const_cast<void*>(records)};
-    launch_linear_chain_groups(f, d->B * d->NH, s);
+    launch_linear_chain_groups(f, n_bh(d), s);
 }
 
 }  // namespace mfma

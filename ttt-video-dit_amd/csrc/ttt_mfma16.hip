@@ -147,13 +147,18 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void linear_scan16_kernel(wv::Lin16
     lin16::forward_part(bk, c, bh);
 }
 
+// Every kernel below but the pair scan's has one form: NAME runs BODY(bk, p, blockIdx.x) with THREADS threads, on a DeviceWave over
+// the workgroup's whole dynamic LDS
+#define WAVE_KERNEL(NAME, THREADS, PARAMS, BODY)                                    \
+    __global__ __launch_bounds__(THREADS) void NAME(PARAMS p) {                      \
+        extern __shared__ __attribute__((aligned(16))) char smem[];                  \
+        DeviceWave bk{smem};                                                         \
+        BODY(bk, p, blockIdx.x);                                                     \
+    }
+
 // TTT-MLP forward scan at mini-batches of 16: the backend-templated workgroup body of ttt_mlp16_body.h, over the whole sequence
 // or a part of it (one kernel for both: the one-call scan is the part [0, NC) without a final-state store)
-__global__ __launch_bounds__(NT16) void mlp_scan16_body_kernel(wv::Mlp16ChunkParams c) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    mlp16::forward_part(bk, c, blockIdx.x);
-}
+WAVE_KERNEL(mlp_scan16_body_kernel, NT16, wv::Mlp16ChunkParams, mlp16::forward_part)
 
 // TTT-MLP forward scan at mini-batches of 16 as a PAIR of workgroups per (b, h) (ttt_mlp16_pair_body.h; opt-in): the device side of
 // the hand-over policy - cdna_hip_programming.md Guideline 16 form R1, as the CS = 64 pair scan (ttt_mfma2.hip).  Record payloads are
@@ -214,167 +219,80 @@ __global__ __launch_bounds__(NT16) void mlp_pair16_kernel(wv::Mlp16ChunkParams c
 // TTT-MLP backward at mini-batches of 16 (ttt_mlp16_bwd_body.h): one workgroup of eight waves per (b, h), each owning a slice of 32 hidden
 // units as in the forward, walks the checkpoint groups from the last to the first: recompute into the caller's *_init_group slots, then
 // the reverse walk.  Explicit TTT_IMPL_MFMA only (capi.hip).
-__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_bwd16_kernel(wv::Mlp16BwdParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    mlp16::bwd::backward(bk, p, blockIdx.x);
-}
+WAVE_KERNEL(mlp_bwd16_kernel, 64 * mlp16::bwd::WAVES, wv::Mlp16BwdParams, mlp16::bwd::backward)
 
 // The same backward in parts (mlp16::bwd::recompute_groups / sweep_groups): the recompute of a range of checkpoint groups, one workgroup
 // per (b, h, group) - any number of them, none waits for another - into the caller's slot workspace, and the reverse walk over the range
 // from those slots, one workgroup per (b, h).  Same LDS map as the one-call kernel.
-__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_recompute16_groups_kernel(wv::Mlp16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    mlp16::bwd::recompute_groups(bk, q, blockIdx.x);
-}
-__global__ __launch_bounds__(64 * mlp16::bwd::WAVES) void mlp_sweep16_groups_kernel(wv::Mlp16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    mlp16::bwd::sweep_groups(bk, q, blockIdx.x);
-}
+WAVE_KERNEL(mlp_recompute16_groups_kernel, 64 * mlp16::bwd::WAVES, wv::Mlp16BwdPartParams, mlp16::bwd::recompute_groups)
+WAVE_KERNEL(mlp_sweep16_groups_kernel, 64 * mlp16::bwd::WAVES, wv::Mlp16BwdPartParams, mlp16::bwd::sweep_groups)
 
 // backward: one wave per workgroup (48 .. 96 scans on 256 CUs: a CU of its own per scan; up to 512 registers per lane)
-__global__ __launch_bounds__(64) void linear_bwd16_kernel(wv::Lin16Params p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin16::backward(bk, p, blockIdx.x);
-}
+WAVE_KERNEL(linear_bwd16_kernel, 64, wv::Lin16Params, lin16::backward)
 
 // TTT-Linear at mini-batches of 64 tokens (ttt_lin64_body.h): one workgroup of four waves per (b, h), one wave per SIMD - up to 512
 // registers per lane.  Runs on an explicit TTT_IMPL_MFMA only (capi.hip: resolve()).  The forward kernel serves the one-call scan
 // and the scan in parts alike, as at mini-batches of 16.
-__global__ __launch_bounds__(64 * lin64::WAVES) void linear_fwd_cs64_kernel(wv::Lin16ChunkParams c) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin64::forward_part(bk, c, blockIdx.x);
-}
-__global__ __launch_bounds__(64 * lin64::WAVES) void linear_bwd_cs64_kernel(wv::Lin16Params p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin64::backward(bk, p, blockIdx.x);
-}
-
+WAVE_KERNEL(linear_fwd_cs64_kernel, 64 * lin64::WAVES, wv::Lin16ChunkParams, lin64::forward_part)
+WAVE_KERNEL(linear_bwd_cs64_kernel, 64 * lin64::WAVES, wv::Lin16Params, lin64::backward)
 
 // The TTT-Linear backward in parts (lin16:: / lin64::recompute_groups, sweep_groups): the recompute of a range of checkpoint groups,
 // one wave (mini-batches of 16) or one four-wave workgroup (of 64) per (b, h, group), and the reverse walk over the range from the
 // slots it left, one per (b, h).  Neither keeps the state that ends a group in LDS: their LDS ends where L_WHI begins.
-__global__ __launch_bounds__(64) void linear_recompute16_groups_kernel(wv::Lin16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin16::recompute_groups(bk, q, blockIdx.x);
-}
-__global__ __launch_bounds__(64) void linear_sweep16_groups_kernel(wv::Lin16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin16::sweep_groups(bk, q, blockIdx.x);
-}
-__global__ __launch_bounds__(64 * lin64::WAVES) void linear_recompute_cs64_groups_kernel(wv::Lin16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin64::recompute_groups(bk, q, blockIdx.x);
-}
-__global__ __launch_bounds__(64 * lin64::WAVES) void linear_sweep_cs64_groups_kernel(wv::Lin16BwdPartParams q) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin64::sweep_groups(bk, q, blockIdx.x);
-}
+WAVE_KERNEL(linear_recompute16_groups_kernel, 64, wv::Lin16BwdPartParams, lin16::recompute_groups)
+WAVE_KERNEL(linear_sweep16_groups_kernel, 64, wv::Lin16BwdPartParams, lin16::sweep_groups)
+WAVE_KERNEL(linear_recompute_cs64_groups_kernel, 64 * lin64::WAVES, wv::Lin16BwdPartParams, lin64::recompute_groups)
+WAVE_KERNEL(linear_sweep_cs64_groups_kernel, 64 * lin64::WAVES, wv::Lin16BwdPartParams, lin64::sweep_groups)
 
 // A third stage of the backward in parts at mini-batches of 16 (lin16::front_groups, chain_groups): the half of every reverse step
 // that does not depend on the carried gradients, one wave per (b, h, step of the range), and the walk that consumes its records,
 // one wave per (b, h).
-__global__ __launch_bounds__(64) void linear_front16_groups_kernel(wv::Lin16BwdFrontParams f) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin16::front_groups(bk, f, blockIdx.x);
-}
-__global__ __launch_bounds__(64) void linear_chain16_groups_kernel(wv::Lin16BwdFrontParams f) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    DeviceWave bk{smem};
-    lin16::chain_groups(bk, f, blockIdx.x);
-}
+WAVE_KERNEL(linear_front16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::front_groups)
+WAVE_KERNEL(linear_chain16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::chain_groups)
+#undef WAVE_KERNEL
 
 }  // namespace v16
 
-static void lin_attr_once() {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::linear_scan16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, v16::LDS_LIN);
-        (void)hipFuncSetAttribute((const void*)v16::linear_bwd16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS_BWD);
-    });
-}
+// Host side: one ttt::launch_lds per kernel (once_per_device.h) - grid, threads and the dynamic LDS, which is also the limit the
+// kernel's attribute is raised to at its first launch on a device.
+constexpr int T_LIN64 = 64 * lin64::WAVES, T_MLP_BWD = 64 * mlp16::bwd::WAVES;
+
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
-    lin_attr_once();
     const int blocks = (n_bh + v16::LIN_WAVES - 1) / v16::LIN_WAVES;
-    hipLaunchKernelGGL(v16::linear_scan16_kernel, dim3(blocks), dim3(64 * v16::LIN_WAVES), v16::LDS_LIN, s, c, n_bh);
+    launch_lds<v16::linear_scan16_kernel>(blocks, 64 * v16::LIN_WAVES, v16::LDS_LIN, s, c, n_bh);
 }
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
-    lin_attr_once();
-    hipLaunchKernelGGL(v16::linear_bwd16_kernel, dim3(n_bh), dim3(64), lin16::WAVE_LDS_BWD, s, p);
-}
-
-static void lin64_attr_once() {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::linear_fwd_cs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::GROUP_LDS);
-        (void)hipFuncSetAttribute((const void*)v16::linear_bwd_cs64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::GROUP_LDS_BWD);
-    });
+    launch_lds<v16::linear_bwd16_kernel>(n_bh, 64, lin16::WAVE_LDS_BWD, s, p);
 }
 void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
-    lin64_attr_once();
-    hipLaunchKernelGGL(v16::linear_fwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS, s, c);
+    launch_lds<v16::linear_fwd_cs64_kernel>(n_bh, T_LIN64, lin64::GROUP_LDS, s, c);
 }
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
-    lin64_attr_once();
-    hipLaunchKernelGGL(v16::linear_bwd_cs64_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::GROUP_LDS_BWD, s, p);
-}
-
-static void lin_parts_attr_once() {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::linear_recompute16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::L_WHI);
-        (void)hipFuncSetAttribute((const void*)v16::linear_sweep16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::L_WHI);
-        (void)hipFuncSetAttribute((const void*)v16::linear_recompute_cs64_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::L_WHI);
-        (void)hipFuncSetAttribute((const void*)v16::linear_sweep_cs64_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin64::L_WHI);
-    });
+    launch_lds<v16::linear_bwd_cs64_kernel>(n_bh, T_LIN64, lin64::GROUP_LDS_BWD, s, p);
 }
 void launch_linear_recompute_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s) {
-    lin_parts_attr_once();
-    if (cs == 16) hipLaunchKernelGGL(v16::linear_recompute16_groups_kernel, dim3(n_bh * q.nk), dim3(64), lin16::L_WHI, s, q);
-    else hipLaunchKernelGGL(v16::linear_recompute_cs64_groups_kernel, dim3(n_bh * q.nk), dim3(64 * lin64::WAVES), lin64::L_WHI, s, q);
+    if (cs == 16) launch_lds<v16::linear_recompute16_groups_kernel>(n_bh * q.nk, 64, lin16::L_WHI, s, q);
+    else launch_lds<v16::linear_recompute_cs64_groups_kernel>(n_bh * q.nk, T_LIN64, lin64::L_WHI, s, q);
 }
 void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_bh, hipStream_t s) {
-    lin_parts_attr_once();
-    if (cs == 16) hipLaunchKernelGGL(v16::linear_sweep16_groups_kernel, dim3(n_bh), dim3(64), lin16::L_WHI, s, q);
-    else hipLaunchKernelGGL(v16::linear_sweep_cs64_groups_kernel, dim3(n_bh), dim3(64 * lin64::WAVES), lin64::L_WHI, s, q);
-}
-
-static void lin_front_attr_once() {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::linear_front16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS);
-        (void)hipFuncSetAttribute((const void*)v16::linear_chain16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lin16::WAVE_LDS_CHAIN);
-    });
+    if (cs == 16) launch_lds<v16::linear_sweep16_groups_kernel>(n_bh, 64, lin16::L_WHI, s, q);
+    else launch_lds<v16::linear_sweep_cs64_groups_kernel>(n_bh, T_LIN64, lin64::L_WHI, s, q);
 }
 void launch_linear_front_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s) {
-    lin_front_attr_once();
-    hipLaunchKernelGGL(v16::linear_front16_groups_kernel, dim3(n_units), dim3(64), lin16::WAVE_LDS, s, f);
+    launch_lds<v16::linear_front16_groups_kernel>(n_units, 64, lin16::WAVE_LDS, s, f);
 }
 void launch_linear_chain_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s) {
-    lin_front_attr_once();
-    hipLaunchKernelGGL(v16::linear_chain16_groups_kernel, dim3(n_bh), dim3(64), lin16::WAVE_LDS_CHAIN, s, f);
+    launch_lds<v16::linear_chain16_groups_kernel>(n_bh, 64, lin16::WAVE_LDS_CHAIN, s, f);
 }
 
-void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*, hipStream_t s) {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::mlp_scan16_body_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::GROUP_LDS);
-    });
-    // a part of the sequence (mlp_forward_chunk): p.NC steps from step p.ck0 of p.NCs, the pointers those of the whole sequence
-    // (at CS = 16 a part may start at any step, so ck0 carries the first STEP, not a checkpoint index).  p.NCs == 0: one call.
+// a part of the sequence (mlp_forward_chunk): p.NC steps from step p.ck0 of p.NCs, the pointers those of the whole sequence
+// (at CS = 16 a part may start at any step, so ck0 carries the first STEP, not a checkpoint index).  p.NCs == 0: one call.
+static wv::Mlp16ChunkParams mlp16_chunk_params(const ScanParams& p) {
     const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
-    const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
-    hipLaunchKernelGGL(v16::mlp_scan16_body_kernel, dim3(n_bh), dim3(v16::NT16), mlp16::GROUP_LDS, s, c);
+    return {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
+}
+void launch_scan_forward_cs16(const ScanParams& p, int n_bh, unsigned long long*, hipStream_t s) {
+    launch_lds<v16::mlp_scan16_body_kernel>(n_bh, v16::NT16, mlp16::GROUP_LDS, s, mlp16_chunk_params(p));
 }
 
 // The pair form of the scan above (opt-in: ttt_hip_mlp_forward_chunk_pair16).  `ws`: scan_pair16_workspace_bytes(n_bh) bytes - the flag
@@ -390,44 +308,24 @@ int launch_scan_forward_pair16(const ScanParams& p, int n_bh, void* ws, hipStrea
     }
     unsigned* err = sweep_error_word();
     if (!err) return -1;
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::mlp_pair16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::pair::PAIR_LDS);
-    });
-    const int NCs = p.NCs ? p.NCs : p.NC, step0 = p.NCs ? p.ck0 : 0;
-    const wv::Mlp16ChunkParams c = {mlp16_params(p), step0, NCs, p.W1f, p.b1f, p.W2f, p.b2f};
     v16::Pair16Params q = {};
     q.flags = (unsigned*)ws;
     q.ring = (char*)ws + mlp16::pair::flags_bytes(n_bh);
     q.err = err;
     q.nbh = n_bh; q.nbh8 = n_bh8;
     (void)hipMemsetAsync(q.flags, 0, mlp16::pair::flags_bytes(n_bh), s);       // the flags restart at 0 for every launch
-    hipLaunchKernelGGL(v16::mlp_pair16_kernel, dim3(n_bh8 + n_bh), dim3(v16::NT16), mlp16::pair::PAIR_LDS, s, c, q);
+    launch_lds<v16::mlp_pair16_kernel>(n_bh8 + n_bh, v16::NT16, mlp16::pair::PAIR_LDS, s, mlp16_chunk_params(p), q);
     return 0;
 }
 
 void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t s) {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::mlp_bwd16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
-    });
-    hipLaunchKernelGGL(v16::mlp_bwd16_kernel, dim3(n_bh), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, p);
-}
-
-static void mlp_parts_attr_once() {
-    static ttt::OncePerDevice done;
-    done.run([&] {
-        (void)hipFuncSetAttribute((const void*)v16::mlp_recompute16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
-        (void)hipFuncSetAttribute((const void*)v16::mlp_sweep16_groups_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, mlp16::bwd::GROUP_LDS_BWD);
-    });
+    launch_lds<v16::mlp_bwd16_kernel>(n_bh, T_MLP_BWD, mlp16::bwd::GROUP_LDS_BWD, s, p);
 }
 void launch_mlp_recompute_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s) {
-    mlp_parts_attr_once();
-    hipLaunchKernelGGL(v16::mlp_recompute16_groups_kernel, dim3(n_bh * q.nk), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, q);
+    launch_lds<v16::mlp_recompute16_groups_kernel>(n_bh * q.nk, T_MLP_BWD, mlp16::bwd::GROUP_LDS_BWD, s, q);
 }
 void launch_mlp_sweep_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s) {
-    mlp_parts_attr_once();
-    hipLaunchKernelGGL(v16::mlp_sweep16_groups_kernel, dim3(n_bh), dim3(64 * mlp16::bwd::WAVES), mlp16::bwd::GROUP_LDS_BWD, s, q);
+    launch_lds<v16::mlp_sweep16_groups_kernel>(n_bh, T_MLP_BWD, mlp16::bwd::GROUP_LDS_BWD, s, q);
 }
 
 }  // namespace mfma

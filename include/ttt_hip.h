@@ -314,6 +314,8 @@ void        ttt_hip_debug_groups_per_chunk(int groups);
  *   "deriver_split"     sweep: 1 (default) = barrier Bc inside the derivers' reverse step; 0 = behind it;
  *   "attn_prio"         attention backward: 1 (default) = a wave-priority raise around one MFMA cluster per kernel; 0 = without;
  *   "scan_pair"         forward scan at mini-batches of 64: 1 (default) = a pair of workgroups per (b,h); 0 = one;
+ *   "lin_split16_chain_alone"  the two-wave TTT-Linear scan (ttt_hip_lin_split16.h): 0 (default); 1 = the output wave keeps only its
+ *                       barriers and XQW is not written - the bench tool's measurement of what the chain wave alone costs;
  *   "sweep_fault"       fault injection for the tests of the hand-over failure path: workgroup 3 of every backward cluster leaves
  *                       before its first hand-over;
  *   "scan_fault"        fault injection: the output-path workgroup of every forward scan pair leaves at once.

@@ -17,6 +17,10 @@ on the opt-in MFMA scan only, --cs64-impl mfma; mini-batches of 16 have an MFMA 
 
     python tools/ttt_layer_bench.py --ssm ttt_linear --cs64-impl mfma --no-grad --parts 0,2,4,8
     python tools/ttt_layer_bench.py --ssm ttt_linear --mini-batch 16 --batch 2 --no-grad --video-length 63sec --parts 0,4,8 [--scan-only]
+
+A variant with "+split" behind it runs with HipLinear.cs16_scan_split on (the two-wave CS = 16 scan), interleaved with the others:
+
+    python tools/ttt_layer_bench.py --ssm ttt_linear --mini-batch 16 --batch 2 --no-grad --parts 0,0+split,4,4+split
 """
 import argparse
 import json
@@ -97,7 +101,7 @@ def scan_only(a, ext, layer, meta, x, L, parts, set_parts, res):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--parts", default="0,2,3,4", help='variants: N parts, "default", each optionally with "+pair" (the CS = 16 pair scan on)')
+    ap.add_argument("--parts", default="0,2,3,4", help='variants: N parts, "default", each optionally with "+pair" (the TTT-MLP CS = 16 pair scan on) or "+split" (the TTT-Linear CS = 16 two-wave scan on)')
     ap.add_argument("--video-length", default="9sec")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mini-batch", type=int, default=64, choices=[64, 16], help="16: the evaluation settings (no scan checkpoints)")
@@ -147,7 +151,8 @@ def main():
     dy = torch.randn(a.batch, L, cfg.model_dim, device=dev, generator=g).bfloat16() * 0.1
     params = [p for p in layer.parameters() if p.requires_grad]
     # a variant: a number of parts or "default", with "+pair" behind it = TTTBase.cs16_scan_pair on for that variant (CS = 16)
-    parts = [v if (v == "default" or v.endswith("+pair")) else int(v) for v in a.parts.split(",")]
+    # ... or "+split" = HipLinear.cs16_scan_split on for that variant (TTT-Linear, CS = 16)
+    parts = [v if (v == "default" or v.endswith("+pair") or v.endswith("+split")) else int(v) for v in a.parts.split(",")]
     res = {"L": L, "batch": a.batch, "mini_batch": a.mini_batch, "ssm": a.ssm, "tuned_gemms": bool(tuned), "by_parts": {}}
     if linear:
         res["cs64_impl"] = HipLinear.cs64_impl
@@ -160,6 +165,10 @@ def main():
         TTTBase.cs16_scan_pair = int(pair)
         if pair:
             n = n[:-5] if n[:-5] == "default" else int(n[:-5])
+        split = isinstance(n, str) and n.endswith("+split")
+        HipLinear.cs16_scan_split = int(split)
+        if split:
+            n = n[:-6] if n[:-6] == "default" else int(n[:-6])
         if linear:
             layer.ttt.linear_pipeline_parts = default_linear if n == "default" else n
         elif n == "default":

@@ -8,6 +8,7 @@
 #include "../../include/ttt_hip_pair16.h"
 #include "../../include/ttt_hip_mlp_bwd_parts.h"
 #include "../../include/ttt_hip_lin_bwd_front.h"
+#include "../../include/ttt_hip_lin_split16.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -116,7 +117,8 @@ int ttt_hip_debug_option(const char* name, int value) {
     else if (!strcmp(name, "attn_prio")) ttt::attn::set_debug_attn_variant(value);               // attention backward: 1 (default) / 0 = without the s_setprio pair per kernel
     else if (!strcmp(name, "sweep_fault")) ttt::mfma::set_debug_sweep_fault(value);              // fault injection: workgroup 3 of every sweep cluster leaves early
     else if (!strcmp(name, "scan_pair")) ttt::mfma::set_debug_scan_pair(value);                  // forward scan at CS = 64: 1 (default) a pair of workgroups per (b,h) / 0 = one
-    else if (!strcmp(name, "scan_fault")) ttt::mfma::set_debug_scan_fault(value);                // fault injection: role B of every scan pair leaves at once
+    else if (!strcmp(name, "lin_split16_chain_alone")) ttt::mfma::set_debug_lin_split16_chain_alone(value);   // two-wave TTT-Linear scan: 0 (default) / 1 = output role's work removed (bench arm)
+    else if (!strcmp(name, "scan_fault"))ttt::mfma::set_debug_scan_fault(value);                // fault injection: role B of every scan pair leaves at once
     else return -1;
     return 0;
 }
@@ -302,6 +304,18 @@ int ttt_hip_linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a
     if (!W1_final != !b1_final) return fail("ttt_hip: linear_forward_chunk: give both final-state buffers or neither");
     ttt::mfma::linear_forward_chunk(d, a, step0, nsteps, W1_final, b1_final, (hipStream_t)stream);
     return post_launch("linear_forward_chunk");
+}
+
+// include/ttt_hip_lin_split16.h
+int ttt_hip_linear_forward_chunk_split16(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1_final,
+                                         float* b1_final, void*, size_t, void* stream) {
+    if (check_linear_fwd_args(d, a)) return -1;
+    if (d->act_dtype != TTT_DTYPE_BF16 || d->F != 64 || d->CS != 16 || resolve(d, false, false) != TTT_IMPL_MFMA)
+        return fail("ttt_hip: linear_forward_chunk_split16: the two-wave scan serves bf16 activations, F = 64, mini-batches of 16 on the MFMA scan only");
+    if (check_steps("linear_forward_chunk_split16", d, step0, nsteps)) return -1;
+    if (!W1_final != !b1_final) return fail("ttt_hip: linear_forward_chunk_split16: give both final-state buffers or neither");
+    ttt::mfma::linear_forward_chunk_split16(d, a, step0, nsteps, W1_final, b1_final, (hipStream_t)stream);
+    return post_launch("linear_forward_chunk_split16");
 }
 
 int ttt_hip_linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* ws, size_t wsb, void* stream) {

@@ -19,6 +19,8 @@ int  mlp_backward(const ttt_dims* d, const ttt_mlp_bwd_args* a, void* ws, hipStr
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void* ws, hipStream_t s);
 void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f,
                           hipStream_t s);                    // CS = 16 or 64; any [step0, step0 + nsteps) inside [0, NC)
+void linear_forward_chunk_split16(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f,
+                                  hipStream_t s);            // CS = 16 only: the two-wave form (include/ttt_hip_lin_split16.h)
 void linear_backward(const ttt_dims* d, const ttt_linear_bwd_args* a, void* ws, hipStream_t s);
 // the TTT-Linear backward in parts (include/ttt_hip_bwd_parts.h): checkpoint groups [k0, k0 + nk) of the sequence `d` / `a` describe
 size_t linear_backward_parts_slots(const ttt_dims* d, int nk);

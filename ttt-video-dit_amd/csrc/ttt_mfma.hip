@@ -123,6 +123,12 @@ void linear_forward_chunk(const ttt_dims* d, const ttt_linear_fwd_args* a, int s
     if (d->CS == 16) launch_linear_forward_cs16(c, n_bh(d), s);
     else launch_linear_forward_cs64(c, n_bh(d), s);
 }
+void linear_forward_chunk_split16(const ttt_dims* d, const ttt_linear_fwd_args* a, int step0, int nsteps, float* W1f, float* b1f,
+                                  hipStream_t s) {
+    wv::Lin16ChunkParams c = {lin16_fwd_params(d, a), step0, d->NC, W1f, b1f};
+    c.p.NC = nsteps;
+    launch_linear_forward_split16(c, n_bh(d), s);
+}
 void linear_forward(const ttt_dims* d, const ttt_linear_fwd_args* a, void*, hipStream_t s) {
     linear_forward_chunk(d, a, 0, d->NC, nullptr, nullptr, s);
 }

@@ -38,6 +38,7 @@
 #include "ttt_mfma_int.h"
 #define TTT_WV_FN __device__ __forceinline__
 #include "ttt_lin16_body.h"
+#include "ttt_lin16_split_body.h"
 #include "ttt_lin64_body.h"
 #include "ttt_mlp16_body.h"
 #include "ttt_mlp16_bwd_body.h"
@@ -249,6 +250,12 @@ WAVE_KERNEL(linear_sweep_cs64_groups_kernel, 64 * lin64::WAVES, wv::Lin16BwdPart
 // one wave per (b, h).
 WAVE_KERNEL(linear_front16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::front_groups)
 WAVE_KERNEL(linear_chain16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::chain_groups)
+
+// The CS = 16 forward scan with its output path on a second wave (ttt_lin16_split_body.h; opt-in): one workgroup of two waves per
+// (b, h) - the chain role and the output role, on two SIMDs of the compute unit, one workgroup barrier per step.  The second kernel
+// is the bench tool's chain-alone arm: the output role keeps only its barriers.
+WAVE_KERNEL(linear_split16_kernel, 64 * lin16::split::WAVES, wv::Lin16ChunkParams, lin16::split::forward_part)
+WAVE_KERNEL(linear_split16_chain_alone_kernel, 64 * lin16::split::WAVES, wv::Lin16ChunkParams, lin16::split::chain_alone_part)
 #undef WAVE_KERNEL
 
 }  // namespace v16
@@ -260,6 +267,13 @@ constexpr int T_LIN64 = 64 * lin64::WAVES, T_MLP_BWD = 64 * mlp16::bwd::WAVES;
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
     const int blocks = (n_bh + v16::LIN_WAVES - 1) / v16::LIN_WAVES;
     launch_lds<v16::linear_scan16_kernel>(blocks, 64 * v16::LIN_WAVES, v16::LDS_LIN, s, c, n_bh);
+}
+static int g_split16_chain_alone = 0;      // DEBUG (tools/lin16_split_bench.py): 1 = the split scan without its output role's work
+void set_debug_lin_split16_chain_alone(int v) { g_split16_chain_alone = v; }
+void launch_linear_forward_split16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s) {
+    constexpr int T = 64 * lin16::split::WAVES;
+    if (g_split16_chain_alone) launch_lds<v16::linear_split16_chain_alone_kernel>(n_bh, T, lin16::split::GROUP_LDS, s, c);
+    else launch_lds<v16::linear_split16_kernel>(n_bh, T, lin16::split::GROUP_LDS, s, c);
 }
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s) {
     launch_lds<v16::linear_bwd16_kernel>(n_bh, 64, lin16::WAVE_LDS_BWD, s, p);

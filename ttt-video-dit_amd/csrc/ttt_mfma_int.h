@@ -56,6 +56,9 @@ void launch_mlp_backward_cs16(const wv::Mlp16BwdParams& p, int n_bh, hipStream_t
 void launch_mlp_recompute_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s);
 void launch_mlp_sweep_groups(const wv::Mlp16BwdPartParams& q, int n_bh, hipStream_t s);
 void launch_linear_forward_cs16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one wave per (b,h); whole sequence or a part
+// the same scan with the output path on a second wave (ttt_lin16_split_body.h, opt-in): one two-wave workgroup per (b,h)
+void launch_linear_forward_split16(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);
+void set_debug_lin_split16_chain_alone(int v);   // DEBUG: 1 = that scan with the output role's work removed (`out` not written), 0 (default)
 void launch_linear_backward_cs16(const wv::Lin16Params& p, int n_bh, hipStream_t s);
 void launch_linear_forward_cs64(const wv::Lin16ChunkParams& c, int n_bh, hipStream_t s);   // TTT-Linear, one 4-wave workgroup per (b,h); whole sequence or a part
 void launch_linear_backward_cs64(const wv::Lin16Params& p, int n_bh, hipStream_t s);

@@ -183,6 +183,11 @@ _PROTOTYPES_LIN_BWD_FRONT = {
     "ttt_hip_linear_front_groups": _sig("2p 2i p z p z p"),
     "ttt_hip_linear_chain_groups": _sig("2p 2i p z p z p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_lin_split16.h, the seventh header: the TTT-Linear forward scan at mini-batches of
+# 16 with its output path on a second wave (tests/test_abi_lin_split16_cpu.py compares the two)
+_PROTOTYPES_LIN_SPLIT16 = {
+    "ttt_hip_linear_forward_chunk_split16": _sig("2p 2i 3p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -205,7 +210,7 @@ def load_library() -> ctypes.CDLL:
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
     for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16,
-                                      **_PROTOTYPES_MLP_BWD_PARTS, **_PROTOTYPES_LIN_BWD_FRONT}.items():
+                                      **_PROTOTYPES_MLP_BWD_PARTS, **_PROTOTYPES_LIN_BWD_FRONT, **_PROTOTYPES_LIN_SPLIT16}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -224,8 +229,8 @@ def debug_timing(buf: Optional[torch.Tensor]) -> None:
 
 def debug_option(name: str, value: int) -> None:
     """DEBUG / A-B knobs by name, described at ttt_hip_debug_option in include/ttt_hip.h: ``groups_per_chunk``, ``overlap_tail``,
-    ``fast_records``, ``sweep_fast_count`` (a query: see ``sweep_fast_count()``), ``deriver_split``, ``attn_prio``, ``scan_pair`` and the
-    fault injections ``sweep_fault``, ``scan_fault``."""
+    ``fast_records``, ``sweep_fast_count`` (a query: see ``sweep_fast_count()``), ``deriver_split``, ``attn_prio``, ``scan_pair``,
+    ``lin_split16_chain_alone`` and the fault injections ``sweep_fault``, ``scan_fault``."""
     if load_library().ttt_hip_debug_option(name.encode(), int(value)) != 0:
         raise ValueError(f"unknown debug option {name!r}")
 
@@ -549,6 +554,40 @@ def ttt_linear_forward_chunk(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_no
     dims, args, device = _scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl)
     # the final state goes where the initial one came from
     _launch("ttt_hip_linear_forward", dims, args, device, suffix="_chunk", extra=(int(step0), int(nsteps), args.W1_init, args.b1_init))
+
+
+linear_split16_calls = {"whole": 0, "chunk": 0}      # launches of this process (tests, tools)
+
+
+def _launch_split16(dims, args, device, step0, nsteps, finals, counter) -> None:
+    """``ttt_hip_linear_forward_chunk_split16`` (include/ttt_hip_lin_split16.h) on the current stream; it has no workspace"""
+    lib = load_library()
+    with torch.cuda.device(device):
+        rc = lib.ttt_hip_linear_forward_chunk_split16(ctypes.byref(dims), ctypes.byref(args), int(step0), int(nsteps), *finals, None, 0,
+                                                      torch.cuda.current_stream(device).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(lib.ttt_hip_last_error().decode())
+    linear_split16_calls[counter] += 1
+
+
+def ttt_linear_forward_split16(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints,
+                               b1_checkpoints, XQW_batch, checkpoint_group_size):
+    """``ttt_linear_forward_impl`` at mini-batches of 16 (bf16, head dim 64, MFMA scan) with the output path on a second wave: one
+    workgroup of two waves per (b, h) - the first carries the state, the second computes the outputs from the packed state the first
+    hands over through LDS (csrc/ttt_lin16_split_body.h; opt-in) - with the bits of ``ttt_linear_forward_impl``.  ``impl``: None,
+    'auto' or 'mfma'; every other geometry, dtype or selector is refused."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_init, b1_init, W1_checkpoints, b1_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl)
+    _launch_split16(dims, args, device, 0, dims.NC, (None, None), "whole")
+
+
+def ttt_linear_forward_chunk_split16(impl, XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W1_checkpoints,
+                                     b1_checkpoints, XQW_batch, checkpoint_group_size, step0, nsteps):
+    """``ttt_linear_forward_chunk`` at mini-batches of 16 in the two-wave form (``ttt_linear_forward_split16``): steps
+    [step0, step0 + nsteps), the fp32 state in ``W1_state`` / ``b1_state`` REPLACED by the state after the last step."""
+    tensors = (XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_state, b1_state, W1_checkpoints, b1_checkpoints, XQW_batch)
+    dims, args, device = _scan_args(_LinFwd, _LIN_FWD_SPEC, tensors, checkpoint_group_size, impl=impl)
+    _launch_split16(dims, args, device, step0, nsteps, (args.W1_init, args.b1_init), "chunk")
 
 
 def ttt_linear_backward(XQ, XK, XV, last_eta, ttt_norm_weight, ttt_norm_bias, W1_checkpoints, b1_checkpoints,

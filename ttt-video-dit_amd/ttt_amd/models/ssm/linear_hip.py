@@ -42,6 +42,31 @@ def _backward_front_default():
     return int(v)
 
 
+def _cs16_scan_split_default():
+    v = os.environ.get("TTT_LINEAR_CS16_SCAN_SPLIT", "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"TTT_LINEAR_CS16_SCAN_SPLIT: expected '0' (off) or '1', got {v!r}")
+    return int(v)
+
+
+def scan_split_applies(ext, impl, XQ, G):
+    """``HipLinear.cs16_scan_split`` is on and this forward is what the two-wave scan serves: bf16, head dim 64, mini-batches of 16, on
+    the MFMA scan, with an extension that has the entry.  Off (the default): nothing is asked of the extension."""
+    v = HipLinear.cs16_scan_split
+    if v not in (0, 1) or isinstance(v, bool):
+        raise ValueError(f"HipLinear.cs16_scan_split: expected 0 or 1, got {v!r}")
+    B, NH, NC, CS, F = XQ.shape
+    if v == 0 or CS != 16 or F != 64 or XQ.dtype != torch.bfloat16 or not hasattr(ext, "ttt_linear_forward_chunk_split16"):
+        return False
+    return ext.resolved_impl(B, NH, NC, CS, F, int(G), XQ.dtype, mlp=False, backward=False, impl=impl) == "mfma"
+
+
+def linear_forward_chunk_call(ext, impl, XQ, G):
+    """the binding's TTT-Linear forward over a part of the sequence for this call: ``ttt_linear_forward_chunk`` unless the split switch
+    applies (same arguments, same bits)"""
+    return ext.ttt_linear_forward_chunk_split16 if scan_split_applies(ext, impl, XQ, G) else ext.ttt_linear_forward_chunk
+
+
 def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     """``ttt_linear_backward`` as ranges of ``gpp`` checkpoint groups, walked from the last range to the first (the entries of
     include/ttt_hip_bwd_parts.h), on the schedule of ``pipeline.run_in_parts``: the recompute of the range to be swept next runs on the
@@ -103,6 +128,12 @@ class HipLinear(torch.autograd.Function):
     # other call is what it is without it.  Same bits either way.  Default from the environment variable TTT_LINEAR_BACKWARD_FRONT, read
     # once at import.
     backward_front = _backward_front_default()
+    # The forward scan at mini-batches of 16 with its output path on a second wave (csrc/ttt_lin16_split_body.h): 0 (default) = the
+    # one-wave scan, 1 = the two-wave form - in one piece here and in the parts of pipeline.py (the chunk picker of
+    # ``pipeline.LINEAR_SCAN``) - where the call is bf16, head dim 64, mini-batches of 16, resolves to the MFMA scan and the extension
+    # has the entry (``scan_split_applies``); every other call is what it is without it.  Same bits either way, so the backward needs
+    # nothing.  Default from the environment variable TTT_LINEAR_CS16_SCAN_SPLIT, read once at import.
+    cs16_scan_split = _cs16_scan_split_default()
 
     @staticmethod
     def _impl(CS, F, act):
@@ -153,7 +184,10 @@ class HipLinear(torch.autograd.Function):
             W1c = torch.empty(B, NH, K, F, F, device=dev, dtype=_F32)
             b1c = torch.empty(B, NH, K, 1, F, device=dev, dtype=_F32)
             W1, b1 = W1_init.to(_F32).contiguous(), b1_init.to(_F32).contiguous()
-            fwd = ext.ttt_linear_forward if ctx.impl is None else (lambda *a: ext.ttt_linear_forward_impl(ctx.impl, *a))
+            if scan_split_applies(ext, ctx.impl, XQ, G):
+                fwd = lambda *a: ext.ttt_linear_forward_split16(ctx.impl, *a)
+            else:
+                fwd = ext.ttt_linear_forward if ctx.impl is None else (lambda *a: ext.ttt_linear_forward_impl(ctx.impl, *a))
             fwd(XQ, XK, XV, last_eta, ln_w, ln_b, W1, b1, W1c, b1c, out, G)
         ctx.save_for_backward(XQ, XV, XK, last_eta, ln_w, ln_b, W1c, b1c)
         ctx.G = G

@@ -228,8 +228,14 @@ def _mlp_chunk(ext, impl):
 
 
 MLP_SCAN = ScanKind("scan", lambda F: ((F, 4 * F), (1, 4 * F), (4 * F, F), (1, F)), lambda NH, F: (1, NH, 1, F), _mlp_chunk)
-LINEAR_SCAN = ScanKind("scan_lin", lambda F: ((F, F), (1, F)), lambda NH, F: (NH, F),
-                       lambda ext, impl: (lambda *a: ext.ttt_linear_forward_chunk(impl, *a)))
+def _lin_chunk(ext, impl):
+    """``ext.ttt_linear_forward_chunk``, or - ``HipLinear.cs16_scan_split`` on, at mini-batches of 16 on the MFMA scan - its two-wave
+    form; picked per call from XQ's shape and the checkpoint group size (arguments: ..., out, G, step0, nsteps)"""
+    from ttt_amd.models.ssm.linear_hip import linear_forward_chunk_call
+    return lambda XQ, *a: linear_forward_chunk_call(ext, impl, XQ, a[-3])(impl, XQ, *a)
+
+
+LINEAR_SCAN = ScanKind("scan_lin", lambda F: ((F, F), (1, F)), lambda NH, F: (NH, F), _lin_chunk)
 
 
 def prepass(ext, x, wq, wk, wv, wo, post_norm, ln_w32, ln_b32, rope, src, pos, n_pos, NH, state, last_eta, G, parts, kind=MLP_SCAN,

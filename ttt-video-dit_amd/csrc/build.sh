@@ -9,7 +9,7 @@ mkdir -p "$OUT" build
 pids=()
 for src in capi ttt_generic ttt_mfma ttt_mfma2 ttt_mfma16 ttt_mfma_bwd2 ttt_mfma_bwd4 ttt_mfma_rc4 ttt_prepost attn_fwd attn_bwd attn_pre attn_v2; do
   # rebuild when the source, any header here or the public header is newer than the object
-  if [ ! -f build/$src.o ] || [ -n "$(find $src.hip *.h ../../include/ttt_hip.h ../../include/ttt_hip_parts.h ../../include/ttt_hip_bwd_parts.h ../../include/ttt_hip_pair16.h ../../include/ttt_hip_mlp_bwd_parts.h ../../include/ttt_hip_lin_bwd_front.h ../../include/ttt_hip_lin_split16.h -newer build/$src.o)" ]; then
+  if [ ! -f build/$src.o ] || [ -n "$(find $src.hip *.h ../../include/ttt_hip.h ../../include/ttt_hip_parts.h ../../include/ttt_hip_bwd_parts.h ../../include/ttt_hip_pair16.h ../../include/ttt_hip_mlp_bwd_parts.h ../../include/ttt_hip_lin_bwd_front.h ../../include/ttt_hip_lin_split16.h ../../include/ttt_hip_lin64_bwd_front.h -newer build/$src.o)" ]; then
     $HIPCC $FLAGS -c $src.hip -o build/$src.o &
     pids+=($!)
   fi

@@ -9,6 +9,7 @@
 #include "../../include/ttt_hip_mlp_bwd_parts.h"
 #include "../../include/ttt_hip_lin_bwd_front.h"
 #include "../../include/ttt_hip_lin_split16.h"
+#include "../../include/ttt_hip_lin64_bwd_front.h"
 #include "ttt_generic.h"
 #include "ttt_mfma.h"
 #include "ttt_prepost.h"
@@ -401,6 +402,40 @@ int ttt_hip_linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a,
     if (check_carry("linear_chain_groups", ln_carry, carry_bytes, ttt::mfma::linear_backward_parts_carry(d), false)) return -1;
     ttt::mfma::linear_chain_groups(d, a, k0, nk, slots, records, ln_carry, (hipStream_t)stream);
     return post_launch("linear_chain_groups");
+}
+
+// include/ttt_hip_lin64_bwd_front.h
+static int check_bwd_front64(const char* fmt_what, const ttt_dims* d, int k0, int nk, const void* slots, size_t slots_bytes,
+                             const void* records, size_t records_bytes) {
+    if (d->CS == 16 && resolve(d, false, true) == TTT_IMPL_MFMA)
+        return fail("ttt_hip: %s: only mini-batches of 64 (on an explicit TTT_IMPL_MFMA) have this front / chain stage; mini-batches of 16 have ttt_hip_lin_bwd_front.h", fmt_what);
+    if (check_bwd_parts(fmt_what, d, k0, nk, slots, slots_bytes)) return -1;
+    if (!records || records_bytes < ttt::mfma::linear_backward_front64_records(d, nk))
+        return fail("ttt_hip: %s: record workspace null or smaller than ttt_hip_linear_backward_front64_records(d, nk)", fmt_what);
+    return 0;
+}
+size_t ttt_hip_linear_backward_front64_records(const ttt_dims* d, int nk) {
+    if (check_dims(d) || nk <= 0 || d->CS != 64 || resolve(d, false, true) != TTT_IMPL_MFMA) return 0;
+    return ttt::mfma::linear_backward_front64_records(d, nk);
+}
+int ttt_hip_linear_front64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
+                                  void* records, size_t records_bytes, void* stream) {
+    if (check_entry(d, a)) return -1;
+    NEED(XQ); NEED(XK); NEED(XV); NEED(ttt_norm_weight); NEED(ttt_norm_bias); NEED(grad_L_XQW); NEED(grad_L_XQ);
+    if (check_bwd_front64("linear_front64_groups", d, k0, nk, slots, slots_bytes, records, records_bytes)) return -1;
+    ttt::mfma::linear_front64_groups(d, a, k0, nk, slots, records, (hipStream_t)stream);
+    return post_launch("linear_front64_groups");
+}
+int ttt_hip_linear_chain64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, size_t slots_bytes,
+                                  const void* records, size_t records_bytes, float* ln_carry, size_t carry_bytes, void* stream) {
+    if (check_entry(d, a)) return -1;
+    NEED(XQ); NEED(XK); NEED(last_eta); NEED(ttt_norm_weight); NEED(ttt_norm_bias);
+    NEED(grad_L_W1_last); NEED(grad_L_b1_last); NEED(grad_L_ttt_norm_weight); NEED(grad_L_ttt_norm_bias);
+    NEED(grad_L_W1_init); NEED(grad_L_b1_init); NEED(grad_L_last_eta); NEED(grad_L_XK); NEED(grad_L_XV);
+    if (check_bwd_front64("linear_chain64_groups", d, k0, nk, slots, slots_bytes, records, records_bytes)) return -1;
+    if (check_carry("linear_chain64_groups", ln_carry, carry_bytes, ttt::mfma::linear_backward_parts_carry(d), false)) return -1;
+    ttt::mfma::linear_chain64_groups(d, a, k0, nk, slots, records, ln_carry, (hipStream_t)stream);
+    return post_launch("linear_chain64_groups");
 }
 
 // include/ttt_hip_mlp_bwd_parts.h

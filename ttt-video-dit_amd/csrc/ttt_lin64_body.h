@@ -1019,5 +1019,394 @@ TTT_WV_FN void sweep_groups(BK& bk, const Lin16BwdPartParams& q, int bh) {
     if (k0 == 0) store_ln_grads(bk, w, p, bh, y);
 }
 
+// ===================================================================================================================
+// A third stage of the backward in parts (Lin16BwdFrontParams, ttt_wave_types.h ; see lin16::front_groups / chain_groups).  The blocks
+// (2), (4) and (1) of reverse_step stand in front of barrier A: every wave runs them on its own 16 token rows from the step's tiles
+// and the two slots, with no exchange between waves.  They are the statements of lin16::front_step on token block 4 * tile + w, so
+// front_groups runs them as ONE WAVE per (b, h, step of the range, token block), on the LDS map of ttt_lin16_body.h - no workgroup,
+// no barrier.  It stores the block's rows of dXQ and leaves the block's record in the field layout of lin16 (REC_*); a step's record
+// is [w][field][lane] (LIN64_FRONT_RECORD_BYTES).  chain_groups is the walk that remains, a workgroup of four waves.
+//
+// inner_grad for front_step, as lin16::inner_grad_pinned - but the walk kernels of THIS body (linear_bwd_cs64_kernel,
+// linear_sweep_cs64_groups_kernel) start the sum of the four products gxh[fb] = go[fb] gamma[fb] of a row the other way round:
+// fma(go0, gamma0, gxh1), where the mini-batch-16 walk has fma(go1, gamma1, gxh0) ; read from their assembly.  The other sums are
+// taken as at mini-batch 16.  (On the host a sum of rounded products either way: same bits.)
+template <class BK>
+TTT_WV_FN void inner_grad_pinned(BK& bk, const f32x4 (&z)[4], const f32x4 (&tg)[4], const float (&gam)[4], const float (&bet)[4], float eps,
+                                 InnerGrad& o) {
+    using lin16::fma4;
+    using lin16::splat4;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) o.xh[fb] = z[fb];
+    o.rstd = lin16::normalize_rows(bk, o.xh, eps);
+    f32x4 gxh[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        o.go[fb] = fma4(splat4(gam[fb]), o.xh[fb], splat4(bet[fb])) - tg[fb];
+        gxh[fb] = o.go[fb] * gam[fb];
+    }
+    f32x4 s1 = fma4(o.go[0], splat4(gam[0]), gxh[1]);                     // gxh[0] + gxh[1] + gxh[2] + gxh[3]
+    s1 = fma4(o.go[2], splat4(gam[2]), s1);
+    s1 = fma4(o.go[3], splat4(gam[3]), s1);
+    f32x4 s2 = fma4(o.xh[0], gxh[0], gxh[1] * o.xh[1]);                   // the same sum of gxh[fb] xh[fb]
+    s2 = fma4(o.xh[2], gxh[2], s2);
+    s2 = fma4(o.xh[3], gxh[3], s2);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { s1[r] = bk.sum16(s1[r]); s2[r] = bk.sum16(s2[r]); }
+    o.s2g = s2;
+    const f32x4 sc = o.rstd * (1.0f / 64.0f);
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) o.gz[fb] = fma4(-o.xh[fb], o.s2g, fma4(splat4(64.0f), gxh[fb], -s1)) * sc;
+}
+
+// blocks (2), (4), (1) of reverse_step for ONE 16-row token block, on the single-wave LDS map of ttt_lin16_body.h: the statements of
+// lin16::front_step with the inner_grad above.  Tiles of the block at Kt, Vt, Qt, Dt ; slot / b1v: the state entering the step,
+// slot_n / b1n: the state after it ; dXQ of the block goes to 16-row tile `blk`, everything the chain needs to `rec`.
+template <class BK>
+TTT_WV_FN void front_step(BK& bk, const Lin16Params& p, const lin16::BwdConsts& c, size_t blk, int Kt, int Vt, int Qt, int Dt,
+                          const char* slot, const char* slot_n, const float (&b1v)[4], const float (&b1n)[4], char* rec) {
+    using namespace lin16;      // (the REC_* fields, st_rec, vec4 and the wave helpers; L_IMG is spelled out: the single-wave map)
+    // ---- (2) outer LayerNorm backward: Z1b = Q W1n + b1n ; dZ1b -----------------------------------------------------------
+    bf16x4 dZbp[4];
+    f32x4 dq[4];                     // starts as dOut (accumulator layout), becomes dQ
+    {
+        const bf16x8 qA0 = rho_read(bk, Qt, 0), qA1 = rho_read(bk, Qt, 32);
+        f32x4 yy[4], dxl[4], t2[4];
+        float addg[4], addb[4], csum[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            f32x4 a = lin16::zero4();
+            a = bk.mma32(qA0, ld_pack(bk, slot_n, fb), a);
+            a = bk.mma32(qA1, ld_pack(bk, slot_n, 4 + fb), a);
+            yy[fb] = a + b1n[fb];
+            dq[fb] = bk.mma16(c.IDP, tr4(bk, Dt, lin16::TS, 0, 16 * fb), lin16::zero4());         // exact dOut
+        }
+        const f32x4 rstdl = normalize_rows(bk, yy, c.eps);                                    // yy <- x_hat of the output LN
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dx = dq[fb] * yy[fb];
+            addg[fb] = dx[0] + dx[1] + dx[2] + dx[3];
+            addb[fb] = dq[fb][0] + dq[fb][1] + dq[fb][2] + dq[fb][3];
+            dxl[fb] = dq[fb] * c.gam[fb];
+            t2[fb] = dxl[fb] * yy[fb];
+        }
+        const f32x4 u1 = rowsum64(bk, dxl), u2 = rowsum64(bk, t2);
+        const f32x4 sc = rstdl * (1.0f / 64.0f);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dzb = (64.0f * dxl[fb] - u1 - yy[fb] * u2) * sc;
+            dZbp[fb] = lin16::pack4(dzb);
+            csum[fb] = colsum16(bk, dzb);
+        }
+        st_rec(bk, rec, REC_DZB, lin16::cat(dZbp[0], dZbp[1]));
+        st_rec(bk, rec, REC_DZB + 1, lin16::cat(dZbp[2], dZbp[3]));
+        st_rec(bk, rec, REC_CSUM, vec4(csum));
+        st_rec(bk, rec, REC_DGAM, vec4(addg));
+        st_rec(bk, rec, REC_DBET, vec4(addb));
+    }
+    // ---- (4) dQ = dOut + dZ1b W1n^T ------------------------------------------------------------------------------------------------
+    {
+        bf16x8 aZ[2];
+        image_of(bk, lin16::L_IMG, dZbp, aZ);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dq[fa] = bk.mma32(aZ[0], ld_pack(bk, slot_n, 8 + fa), dq[fa]);
+            dq[fa] = bk.mma32(aZ[1], ld_pack(bk, slot_n, 12 + fa), dq[fa]);
+        }
+        store_rows(bk, lin16::L_IMG + lin16::IMG_BYTES, dq, p.dXQ + blk * 1024);
+    }
+    bk.lds_fence();
+    // ---- (1) inner forward of the step: Z1 = K W + b, LN / L2 gradient ------------------------------------------------
+    const bf16x8 kA0 = rho_read(bk, Kt, 0), kA1 = rho_read(bk, Kt, 32);
+    lin16::InnerGrad ig;
+    {
+        f32x4 z[4], tg[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const bf16x4 kT = tr4(bk, Kt, lin16::TS, 0, 16 * fb);
+            f32x4 a = lin16::zero4();
+            a = bk.mma32(kA0, ld_pack(bk, slot, fb), a);
+            a = bk.mma32(kA1, ld_pack(bk, slot, 4 + fb), a);
+            z[fb] = a + b1v[fb];
+            tg[fb] = bk.mma16(c.IDN, kT, bk.mma16(c.IDP, tr4(bk, Vt, lin16::TS, 0, 16 * fb), lin16::zero4()));   // exact V - K
+        }
+        lin64::inner_grad_pinned(bk, z, tg, c.gam, c.bet, c.eps, ig);
+    }
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        st_rec(bk, rec, REC_XH + fb, ig.xh[fb]);
+        st_rec(bk, rec, REC_GO + fb, ig.go[fb]);
+        st_rec(bk, rec, REC_GZ + fb, ig.gz[fb]);
+    }
+    st_rec(bk, rec, REC_RSTD, ig.rstd);
+    st_rec(bk, rec, REC_S2G, ig.s2g);
+}
+
+// wave `unit` = (bh * (steps of the range) + j) * 4 + w runs the front of token block w of step k0 * G + j of (b, h) = bh
+template <class BK>
+TTT_WV_FN void front_groups(BK& bk, const Lin16BwdFrontParams& f, int unit) {
+    const Lin16BwdPartParams& q = f.q;
+    const Lin16Params& p = q.p;
+    const int NC = p.NC, G = p.G;
+    const int s_lo = q.k0 * G, s_hi = ((q.k0 + q.nk) * G < NC) ? (q.k0 + q.nk) * G : NC, ns = s_hi - s_lo;
+    const int w = unit % WAVES, su = unit / WAVES;
+    const int bh = su / ns, it = s_lo + su % ns, k = it / G, lo = k * G, head = bh % p.NH;
+    const int i = bk.lane() & 15;
+    const size_t blk = ((size_t)bh * NC + it) * WAVES + w;                                          // the [16][64] tile of the block
+    const size_t cell = (size_t)bh * q.nk + (k - q.k0);                                             // (b, h, group of the range)
+    const char* slot = q.slots + (cell * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;                // state entering the step
+    const char* slot_n = slot + LIN_PART_SLOT_BYTES;                                                // ... and after it
+    char* rec = f.records + (cell * G + (it - lo)) * LIN64_FRONT_RECORD_BYTES + (size_t)w * LIN_FRONT_RECORD_BYTES;
+
+    lin16::BwdConsts c;
+    lin16::bwd_consts(bk, p, head, c);
+    Stage sk, sv, sq, sd;
+    lin16::stage_request(bk, sk, p.XK + blk * 1024);
+    lin16::stage_request(bk, sv, p.XV + blk * 1024);
+    lin16::stage_request(bk, sq, p.XQ + blk * 1024);
+    lin16::stage_request(bk, sd, p.dOut + blk * 1024);
+    float b1v[4], b1n[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        b1v[fb] = reinterpret_cast<const float*>(slot + SLOT_BYTES)[16 * fb + i];
+        b1n[fb] = reinterpret_cast<const float*>(slot_n + SLOT_BYTES)[16 * fb + i];
+    }
+    lin16::stage_park(bk, sk, lin16::L_K); lin16::stage_park(bk, sv, lin16::L_V);
+    lin16::stage_park(bk, sq, lin16::L_Q); lin16::stage_park(bk, sd, lin16::L_D);
+    bk.lds_fence();
+    lin64::front_step(bk, p, c, blk, lin16::L_K, lin16::L_V, lin16::L_Q, lin16::L_D, slot, slot_n, b1v, b1n, rec);
+}
+
+// The chain keeps the LDS map of the sweep (the V and dOut tiles and L_WHI unused).  A step's record does not fit the LDS that is
+// left twice, and a wave has its SIMD - 512 registers - to itself: wave w holds its block's record of the step at hand in registers
+// (what reverse_step holds as `ig`, plus dZ1b and the addends until they are published in front of barrier A) and fetches the record
+// of the step in front into a second set while the step runs.
+constexpr int GROUP_LDS_CHAIN = L_WHI;
+static_assert(GROUP_LDS_CHAIN <= 160 * 1024, "LDS budget");
+struct StepRecord {
+    u32x4 f[lin16::REC_FIELDS];
+};
+template <class BK>
+TTT_WV_FN void rec_request(BK& bk, int l, const char* rec, StepRecord& r) {
+#pragma unroll
+    for (int j = 0; j < lin16::REC_FIELDS; ++j) r.f[j] = *reinterpret_cast<const u32x4*>(rec + ((size_t)j * 64 + l) * 16);
+}
+TTT_WV_FN f32x4 rec_f32(const StepRecord& r, int j) { return __builtin_bit_cast(f32x4, r.f[j]); }
+
+// reverse_step without its blocks (2), (4), (1): their results come from the block's record `r`.  Kb, Qb: the K / Q tiles of the
+// mini-batch, eta_off: this wave's eta ; slot: the state entering the step (its transposed packs 8..15 only).  `mid()` runs between
+// barriers A and B, as in reverse_step.  Ends with the carried update (10); the caller fences LDS behind it.
+template <class BK, class Mid>
+TTT_WV_FN void chain_step(BK& bk, int l, int w, const Lin16Params& p, const Consts& c, BwdCarry& y, size_t tile, int Kb, int Qb, int eta_off,
+                          const char* slot, const StepRecord& r, Mid&& mid) {
+    const int g = l >> 4, i = l & 15;
+    const int IMG = L_IMG + w * 2 * IMG_BYTES, own = w * TILE_B;
+    const int Kt = Kb + own;
+    const f32x4 eta4 = bk.template lds<f32x4>(eta_off + 4 * g * 4);
+    // ---- what (2) left: the addends of the carry ; dZ1b -> L_X, its column sums -> L_PS ------------------------------------------
+    {
+        const f32x4 addg = rec_f32(r, lin16::REC_DGAM), addb = rec_f32(r, lin16::REC_DBET), csum = rec_f32(r, lin16::REC_CSUM);
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            y.dgam[fb] += addg[fb];
+            y.dbet[fb] += addb[fb];
+        }
+        const bf16x8 d01 = __builtin_bit_cast(bf16x8, r.f[lin16::REC_DZB]), d23 = __builtin_bit_cast(bf16x8, r.f[lin16::REC_DZB + 1]);
+        const bf16x4 dZbp[4] = {__builtin_shufflevector(d01, d01, 0, 1, 2, 3), __builtin_shufflevector(d01, d01, 4, 5, 6, 7),
+                                __builtin_shufflevector(d23, d23, 0, 1, 2, 3), __builtin_shufflevector(d23, d23, 4, 5, 6, 7)};
+        const float cs[4] = {csum[0], csum[1], csum[2], csum[3]};
+        publish_rows(bk, w, L_X, L_PS, dZbp, cs);
+    }
+    // ---- what (1) left ------------------------------------------------------------------------------------------------------------
+    InnerGrad ig;
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) {
+        ig.xh[fb] = rec_f32(r, lin16::REC_XH + fb);
+        ig.go[fb] = rec_f32(r, lin16::REC_GO + fb);
+        ig.gz[fb] = rec_f32(r, lin16::REC_GZ + fb);
+    }
+    ig.rstd = rec_f32(r, lin16::REC_RSTD);
+    ig.s2g = rec_f32(r, lin16::REC_S2G);
+    const bf16x8 kA0 = lin16::rho_read(bk, Kt, 0), kA1 = lin16::rho_read(bk, Kt, 32);
+    bf16x4 kT[4];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) kT[fb] = lin16::tr4(bk, Kt, TS, 0, 16 * fb);
+    bk.barrier();                                               // A: L_X, L_PS written | read ; every wave has left the step before
+    // ---- (3) dW1n += Q^T dZ1b ; db1n += colsum dZ1b ; the images of dW1n -----------------------------------------------------
+    update_slice(bk, w, Qb, L_X, L_PS, y.dWt, y.db);
+    {
+        bf16x8 mine[2];
+        publish_slice(bk, w, y.dWt, mine);
+        publish_transposed(bk, w, y.dWt);
+    }
+    mid();
+    bk.barrier();                                               // B: L_WI, L_TR written | read (until A of the next step)
+    // ---- (6) dgZ1 = -eta (K dW1n + db1n) ; (8) backward of the fused LN / L2 gradient -> dZ1, dt, dgamma, dbeta -----------------
+    bf16x4 dZ1p[4];
+    f32x4 dk[4];                     // starts as -dt (dt = gradient w.r.t. the target V - K = dV)
+    {
+        f32x4 dgz[4], mGr[4], t2[4];
+        {
+            bf16x8 DWp[8];
+            load_image(bk, DWp);
+#pragma unroll
+            for (int fb = 0; fb < 4; ++fb) {
+                f32x4 a = zero4();
+                a = bk.mma32(kA0, DWp[fb], a);
+                a = bk.mma32(kA1, DWp[4 + fb], a);
+                dgz[fb] = (a + y.db[fb]) * (-eta4);
+                mGr[fb] = dgz[fb] * (-ig.rstd);
+                t2[fb] = mGr[fb] * ig.xh[fb];
+            }
+        }
+        const f32x4 s1 = lin16::rowsum64(bk, mGr) * (1.0f / 64.0f), s2 = lin16::rowsum64(bk, t2) * (1.0f / 64.0f);
+        const f32x4 c2 = ig.s2g * (1.0f / 64.0f);
+        f32x4 dxh[4], dstd[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dgxh = lin16::fma4(dgz[fb], ig.rstd, s1) + ig.xh[fb] * s2;
+            const f32x4 dy = dgxh * c.gam[fb];
+            const f32x4 dg = lin16::fma4(ig.go[fb], dgxh, dy * ig.xh[fb]);
+            y.dgam[fb] += dg[0] + dg[1] + dg[2] + dg[3];
+            y.dbet[fb] += dy[0] + dy[1] + dy[2] + dy[3];
+            dk[fb] = dy;                                                                       // = -dt
+            dxh[fb] = lin16::fma4(ig.go[fb] * c.gam[fb], s2, dy * c.gam[fb]) + mGr[fb] * c2;
+            dstd[fb] = lin16::fma4(dgz[fb], ig.gz[fb], dxh[fb] * ig.xh[fb]) * (-ig.rstd);
+        }
+        const f32x4 v1 = lin16::rowsum64(bk, dxh) * (1.0f / 64.0f), v2 = lin16::rowsum64(bk, dstd) * (1.0f / 64.0f);
+        float cs[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) {
+            const f32x4 dz1 = lin16::fma4(dxh[fb] - v1, ig.rstd, ig.xh[fb] * v2);
+            dZ1p[fb] = pack4(dz1);
+            cs[fb] = lin16::colsum16(bk, dz1);
+        }
+        publish_rows(bk, w, L_X2, L_PS2, dZ1p, cs);                                               // for (10)
+        f32x4 dv[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) dv[fb] = -dk[fb];
+        lin16::store_rows(bk, IMG + IMG_BYTES, dv, p.dXV + tile * 4096 + w * 1024);              // dV = dt
+    }
+    bk.lds_fence();
+    // ---- (5, 7, 9) A1 = gZ1 dW1n^T ; d eta ; dK = -eta A1 - dt + dZ1 W^T --------------------------------------------------------------
+    {
+        bf16x4 gzq[4];
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) gzq[fb] = pack4(ig.gz[fb]);
+        bf16x8 aG[2];
+        lin16::image_of(bk, IMG, gzq, aG);
+        f32x4 acc[4];
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            f32x4 a1 = zero4();
+            a1 = bk.mma32(aG[0], transposed_frag(bk, 0, 16 * fa), a1);
+            a1 = bk.mma32(aG[1], transposed_frag(bk, 1, 16 * fa), a1);
+            dk[fa] -= a1 * eta4;
+            const f32x4 kc = bk.mma16(c.IDP, kT[fa], zero4());                                // exact K, accumulator layout
+            acc[fa] = lin16::fma4(ig.gz[fa], lin16::splat4(y.db[fa]), kc * a1);
+        }
+        const f32x4 de = lin16::rowsum64(bk, acc);
+        if (i == 0) *reinterpret_cast<bf16x4*>(p.deta + tile * 64 + 16 * w + 4 * g) = pack4(-de);
+    }
+    bk.lds_fence();
+    {
+        bf16x8 aD[2];
+        lin16::image_of(bk, IMG, dZ1p, aD);
+#pragma unroll
+        for (int fa = 0; fa < 4; ++fa) {
+            dk[fa] = bk.mma32(aD[0], lin16::ld_pack(bk, slot, 8 + fa), dk[fa]);
+            dk[fa] = bk.mma32(aD[1], lin16::ld_pack(bk, slot, 12 + fa), dk[fa]);
+        }
+        lin16::store_rows(bk, IMG + IMG_BYTES, dk, p.dXK + tile * 4096 + w * 1024);
+    }
+    bk.barrier();                                               // C: L_X2, L_PS2 written | read (until B of the next step)
+    // ---- (10) dW1 = dW1n + K^T dZ1 ; db1 = db1n + colsum dZ1 --------------------------------------------------------------------------
+    update_slice(bk, w, Kb, L_X2, L_PS2, y.dWt, y.db);
+}
+
+// the walk of (b, h) = bh over the groups k0 + nk - 1 .. k0 from the slots recompute_groups and the records front_groups left: the
+// loop and the carry contract of sweep_groups (dW1_last / db1_last -> dW1 / db1, which may alias ; ln_carry ; dln_w / dln_b in the
+// range with k0 == 0) around chain_step.  K, Q, eta and the record of the step in front are fetched while a step runs - none of their
+// addresses depends on the carry.  No V, no dOut.
+template <class BK>
+TTT_WV_FN void chain_groups(BK& bk, const Lin16BwdFrontParams& f, int bh) {
+    const Lin16BwdPartParams& q = f.q;
+    const Lin16Params& p = q.p;
+    const int l0 = bk.lane(), w = bk.wave();
+    const int NC = p.NC, G = p.G, K = p.K, head = bh % p.NH;
+    const int k0 = q.k0, nk = q.nk;
+    const int s_lo = k0 * G, s_hi = ((k0 + nk) * G < NC) ? (k0 + nk) * G : NC;      // the steps [s_lo, s_hi)
+    const size_t tile0 = (size_t)bh * NC;
+    const int ETA = L_ETA + w * 128, own = w * TILE_B;
+    const char* slots = q.slots + (size_t)bh * nk * (G + 1) * LIN_PART_SLOT_BYTES;
+    const char* recs = f.records + (size_t)bh * nk * G * LIN64_FRONT_RECORD_BYTES + (size_t)w * LIN_FRONT_RECORD_BYTES;
+    float* carry = q.ln_carry + (size_t)bh * LIN_PART_CARRY_FLOATS * 64 * WAVES + w * 64 + l0;
+
+    Consts c;
+    make_consts(bk, p, head, c);
+    BwdCarry y;
+    load_slice(bk, w, p.dW1_last + (size_t)bh * 64 * 64, y.dWt);
+    lin16::load_row(bk, p.db1_last + (size_t)bh * 64, y.db);
+    if (k0 + nk == K) {      // the range that ends the sequence starts the sums
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) y.dgam[fb] = y.dbet[fb] = 0.f;
+    } else {
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) { y.dgam[fb] = carry[fb * 64 * WAVES]; y.dbet[fb] = carry[(4 + fb) * 64 * WAVES]; }
+    }
+    int k = k0 + nk - 1, lo = k * G;          // the group of step `it`
+    int cur = 0;
+    Stage sk, sq;
+    unsigned short pe = 0;
+    StepRecord r, rn;
+    {   // the first step of the walk.  Every wave its own rows; the rows of other waves are read behind barrier A of the first step
+        // at the earliest (Q in (3), K in (10)).
+        const size_t t = tile0 + s_hi - 1;
+        lin16::stage_request(bk, sk, p.XK + t * 4096 + w * 1024);
+        lin16::stage_request(bk, sq, p.XQ + t * 4096 + w * 1024);
+        pe = *reinterpret_cast<const unsigned short*>(p.eta + t * 64 + 16 * w + (l0 & 15));
+        rec_request(bk, l0, recs + ((size_t)(k - k0) * G + (s_hi - 1 - lo)) * LIN64_FRONT_RECORD_BYTES, r);
+        park(bk, sk, L_K + own); park(bk, sq, L_Q + own);
+        park_eta(bk, pe, ETA);
+        bk.lds_fence();
+    }
+    for (int it = s_hi - 1; it >= s_lo; --it) {
+        if (it < lo) { --k; lo -= G; }
+        const int l = bk.opaque(l0);
+        const bool more = it > s_lo;
+        if (more) {
+            const size_t t = tile0 + it - 1;
+            const int kn = (it - 1 < lo) ? k - 1 : k, lon = (it - 1 < lo) ? lo - G : lo;      // the group of the step in front
+            lin16::stage_request(bk, sk, p.XK + t * 4096 + w * 1024);
+            lin16::stage_request(bk, sq, p.XQ + t * 4096 + w * 1024);
+            pe = *reinterpret_cast<const unsigned short*>(p.eta + t * 64 + 16 * w + (l & 15));
+            rec_request(bk, l, recs + ((size_t)(kn - k0) * G + (it - 1 - lon)) * LIN64_FRONT_RECORD_BYTES, rn);
+        }
+        const char* slot = slots + ((size_t)(k - k0) * (G + 1) + (it - lo)) * LIN_PART_SLOT_BYTES;       // state entering the step
+        chain_step(bk, l, w, p, c, y, tile0 + it, L_K + cur * T64_B, L_Q + cur * T64_B, ETA + cur * 64, slot, r, [&] {
+            if (more) {      // the other buffer was last read (K in (10), Q in (3)) by the step before this one
+                const int nb = cur ^ 1;
+                park(bk, sk, L_K + nb * T64_B + own); park(bk, sq, L_Q + nb * T64_B + own);
+                park_eta(bk, pe, ETA + nb * 64);
+            }
+        });
+        if (more) {
+            cur ^= 1;
+            r = rn;
+        }
+        bk.lds_fence();
+    }
+    // ---- hand-over, as in sweep_groups: q.p.dW1 / db1 may alias dW1_last / db1_last (every wave reads db1_last and its own slice of
+    // dW1_last in front of the step loop, these stores come behind the barriers of the last step) ; ln_carry is read and written by
+    // the same lane only
+    store_slice(bk, w, p.dW1 + (size_t)bh * 64 * 64, y.dWt);
+    if (w == 0 && (l0 >> 4) == 0)
+#pragma unroll
+        for (int fb = 0; fb < 4; ++fb) p.db1[(size_t)bh * 64 + 16 * fb + (l0 & 15)] = y.db[fb];
+#pragma unroll
+    for (int fb = 0; fb < 4; ++fb) { carry[fb * 64 * WAVES] = y.dgam[fb]; carry[(4 + fb) * 64 * WAVES] = y.dbet[fb]; }
+    if (k0 == 0) store_ln_grads(bk, w, p, bh, y);
+}
+
 }  // namespace lin64
 }  // namespace ttt

@@ -32,6 +32,11 @@ size_t linear_backward_front_records(const ttt_dims* d, int nk);
 void linear_front_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, void* records, hipStream_t s);
 void linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, const void* records,
                          float* ln_carry, hipStream_t s);
+// ... and at mini-batches of 64 (include/ttt_hip_lin64_bwd_front.h)
+size_t linear_backward_front64_records(const ttt_dims* d, int nk);
+void linear_front64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, void* records, hipStream_t s);
+void linear_chain64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, const void* records,
+                           float* ln_carry, hipStream_t s);
 // the TTT-MLP backward at mini-batches of 16 in parts (include/ttt_hip_mlp_bwd_parts.h): checkpoint groups [k0, k0 + nk)
 size_t mlp_backward_parts_slots(const ttt_dims* d, int nk);
 size_t mlp_backward_parts_carry(const ttt_dims* d);

@@ -182,6 +182,21 @@ void linear_chain_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0
                                        (char*)const_cast<void*>(records)};
     launch_linear_chain_groups(f, n_bh(d), s);
 }
+// The same stage at mini-batches of 64: a step's record is the records of its four 16-row token blocks, one front wave each.
+size_t linear_backward_front64_records(const ttt_dims* d, int nk) {
+    return (size_t)d->B * d->NH * (size_t)nk * (size_t)d->G * wv::LIN64_FRONT_RECORD_BYTES;
+}
+void linear_front64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, void* records, hipStream_t s) {
+    const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), nullptr}, (char*)records};
+    const int s_hi = (k0 + nk) * d->G < d->NC ? (k0 + nk) * d->G : d->NC;
+    launch_linear_front64_groups(f, n_bh(d) * (s_hi - k0 * d->G) * 4, s);
+}
+void linear_chain64_groups(const ttt_dims* d, const ttt_linear_bwd_args* a, int k0, int nk, const void* slots, const void* records,
+                           float* ln_carry, hipStream_t s) {
+    const wv::Lin16BwdFrontParams f = {{linear_bwd_params(d, a), k0, nk, (char*)const_cast<void*>(slots), ln_carry},
+                                       (char*)const_cast<void*>(records)};
+    launch_linear_chain64_groups(f, n_bh(d), s);
+}
 
 }  // namespace mfma
 }  // namespace ttt

@@ -251,6 +251,11 @@ WAVE_KERNEL(linear_sweep_cs64_groups_kernel, 64 * lin64::WAVES, wv::Lin16BwdPart
 WAVE_KERNEL(linear_front16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::front_groups)
 WAVE_KERNEL(linear_chain16_groups_kernel, 64, wv::Lin16BwdFrontParams, lin16::chain_groups)
 
+// The same stage at mini-batches of 64 (lin64::front_groups, chain_groups): the front as one wave per (b, h, step of the range,
+// 16-row token block) on the LDS map of the mini-batch-16 body, the chain as one four-wave workgroup per (b, h).
+WAVE_KERNEL(linear_front_cs64_groups_kernel, 64, wv::Lin16BwdFrontParams, lin64::front_groups)
+WAVE_KERNEL(linear_chain_cs64_groups_kernel, 64 * lin64::WAVES, wv::Lin16BwdFrontParams, lin64::chain_groups)
+
 // The CS = 16 forward scan with its output path on a second wave (ttt_lin16_split_body.h; opt-in): one workgroup of two waves per
 // (b, h) - the chain role and the output role, on two SIMDs of the compute unit, one workgroup barrier per step.  The second kernel
 // is the bench tool's chain-alone arm: the output role keeps only its barriers.
@@ -297,6 +302,12 @@ void launch_linear_front_groups(const wv::Lin16BwdFrontParams& f, int n_units, h
 }
 void launch_linear_chain_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s) {
     launch_lds<v16::linear_chain16_groups_kernel>(n_bh, 64, lin16::WAVE_LDS_CHAIN, s, f);
+}
+void launch_linear_front64_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s) {
+    launch_lds<v16::linear_front_cs64_groups_kernel>(n_units, 64, lin16::WAVE_LDS, s, f);
+}
+void launch_linear_chain64_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s) {
+    launch_lds<v16::linear_chain_cs64_groups_kernel>(n_bh, T_LIN64, lin64::GROUP_LDS_CHAIN, s, f);
 }
 
 // a part of the sequence (mlp_forward_chunk): p.NC steps from step p.ck0 of p.NCs, the pointers those of the whole sequence

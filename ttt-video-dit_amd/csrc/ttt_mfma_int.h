@@ -68,6 +68,9 @@ void launch_linear_sweep_groups(const wv::Lin16BwdPartParams& q, int cs, int n_b
 // ... and its third stage at mini-batches of 16: front grid n_units = n_bh * (steps of the range), chain grid n_bh
 void launch_linear_front_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s);
 void launch_linear_chain_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s);
+// ... and at mini-batches of 64: front grid n_units = n_bh * (steps of the range) * 4 single waves, chain grid n_bh workgroups
+void launch_linear_front64_groups(const wv::Lin16BwdFrontParams& f, int n_units, hipStream_t s);
+void launch_linear_chain64_groups(const wv::Lin16BwdFrontParams& f, int n_bh, hipStream_t s);
 void set_debug_dump(float* buf);
 unsigned long long* get_debug_timing();
 void set_debug_overlap_tail(int v);   // backward schedule: 0 one stream, 1 tail of chunk c beside the sweep of chunk c-1, 2 (default) the next recompute too

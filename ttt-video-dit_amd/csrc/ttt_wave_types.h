@@ -71,6 +71,10 @@ struct Lin16BwdFrontParams {
     Lin16BwdPartParams q;
     char* records;
 };
+// the same stage at mini-batches of 64 (ttt_lin64_body.h: front_groups, chain_groups), with the same parameter block: a step's
+// record is the four records of its 16-row token blocks, [w][field][lane] - each in the layout above, written by the wave that runs
+// the front of block w and read by wave w of the chain.
+constexpr size_t LIN64_FRONT_RECORD_BYTES = 4 * LIN_FRONT_RECORD_BYTES;        // 77 824
 
 // arguments of the TTT-MLP forward scan at mini-batches of 16 tokens (F = 64, hidden 256)
 struct Mlp16Params {

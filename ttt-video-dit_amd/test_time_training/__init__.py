@@ -188,6 +188,13 @@ _PROTOTYPES_LIN_BWD_FRONT = {
 _PROTOTYPES_LIN_SPLIT16 = {
     "ttt_hip_linear_forward_chunk_split16": _sig("2p 2i 3p z p"),
 }
+# ... and of every symbol declared in include/ttt_hip_lin64_bwd_front.h, the eighth header: the front / chain stage of the TTT-Linear
+# backward in parts at mini-batches of 64 (tests/test_abi_lin64_bwd_front_cpu.py compares the two)
+_PROTOTYPES_LIN64_BWD_FRONT = {
+    "ttt_hip_linear_backward_front64_records": _sig("p i", ctypes.c_size_t),
+    "ttt_hip_linear_front64_groups": _sig("2p 2i p z p z p"),
+    "ttt_hip_linear_chain64_groups": _sig("2p 2i p z p z p z p"),
+}
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -210,7 +217,8 @@ def load_library() -> ctypes.CDLL:
     if lib.ttt_hip_abi_version() != ABI_VERSION:
         raise RuntimeError(f"test_time_training: libttt_hip.so ABI version {lib.ttt_hip_abi_version()}, this binding needs {ABI_VERSION}: rebuild (csrc/build.sh)")
     for name, (restype, argtypes) in {**_PROTOTYPES, **_PROTOTYPES_PARTS, **_PROTOTYPES_BWD_PARTS, **_PROTOTYPES_PAIR16,
-                                      **_PROTOTYPES_MLP_BWD_PARTS, **_PROTOTYPES_LIN_BWD_FRONT, **_PROTOTYPES_LIN_SPLIT16}.items():
+                                      **_PROTOTYPES_MLP_BWD_PARTS, **_PROTOTYPES_LIN_BWD_FRONT, **_PROTOTYPES_LIN_SPLIT16,
+                                      **_PROTOTYPES_LIN64_BWD_FRONT}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -715,6 +723,30 @@ def ttt_linear_chain_groups(impl, *call):
     nk, slots, records, ln_carry; XV, grad_L_XQW, grad_L_XQ, the checkpoints and ``*_init_group`` may be None.  The caller orders
     recompute -> front -> chain of a range (same stream, or events)."""
     _groups_call("ttt_hip_linear_chain_groups", _LinBwd, _LIN_BWD_SPEC, _LIN_CHAIN_UNUSED, impl, call,
+                 ("slots", "records", "ln_carry"), (linear_bwd_front_calls, "chain"))
+
+
+# The same stage at mini-batches of 64 (include/ttt_hip_lin64_bwd_front.h): the same tensor lists, a record of 4 x 19456 bytes per step.
+def linear_backward_front64_records(B, NH, NC, CS, F, G, nk, act_dtype=torch.bfloat16, *, impl=None) -> int:
+    """bytes of the record workspace of ``ttt_linear_front64_groups`` / ``ttt_linear_chain64_groups`` for ``nk`` checkpoint groups:
+    B * NH * nk * G records of 77824 bytes ; 0 for anything but bf16, F = 64, CS = 64 with ``impl="mfma"``"""
+    return _parts_bytes("ttt_hip_linear_backward_front64_records", B, NH, NC, CS, F, G, act_dtype, impl, nk)
+
+
+def ttt_linear_front64_groups(impl, *call):
+    """``ttt_linear_front_groups`` at mini-batches of 64 (``ttt_hip_linear_front64_groups``): one wave per 16-row token block of every
+    step of the checkpoint groups [k0, k0 + nk), from the ``slots`` ``ttt_linear_recompute_groups`` left for the same range; writes
+    ``grad_L_XQ`` of those steps and one record per step into ``records`` (``linear_backward_front64_records`` bytes).  Same ``call``
+    list; ``impl="mfma"`` only."""
+    _groups_call("ttt_hip_linear_front64_groups", _LinBwd, _LIN_BWD_SPEC, frozenset(LIN_BWD_FIELDS) - _LIN_FRONT_FIELDS, impl, call,
+                 ("slots", "records"), (linear_bwd_front_calls, "front"))
+
+
+def ttt_linear_chain64_groups(impl, *call):
+    """``ttt_linear_chain_groups`` at mini-batches of 64 (``ttt_hip_linear_chain64_groups``): the reverse walk over the checkpoint
+    groups k0 + nk - 1 .. k0 from the ``slots`` and the ``records`` of the same range - the carries and the bits of
+    ``ttt_linear_sweep_groups`` at mini-batches of 64.  Same ``call`` list; ``impl="mfma"`` only."""
+    _groups_call("ttt_hip_linear_chain64_groups", _LinBwd, _LIN_BWD_SPEC, _LIN_CHAIN_UNUSED, impl, call,
                  ("slots", "records", "ln_carry"), (linear_bwd_front_calls, "chain"))
 
 

@@ -42,6 +42,13 @@ def _backward_front_default():
     return int(v)
 
 
+def _backward_front64_default():
+    v = os.environ.get("TTT_LINEAR_BACKWARD_FRONT64", "0")
+    if v not in ("0", "1"):
+        raise ValueError(f"TTT_LINEAR_BACKWARD_FRONT64: expected '0' (off) or '1', got {v!r}")
+    return int(v)
+
+
 def _cs16_scan_split_default():
     v = os.environ.get("TTT_LINEAR_CS16_SCAN_SPLIT", "0")
     if v not in ("0", "1"):
@@ -78,7 +85,9 @@ def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     the allocator's reuse of the blocks).
     ``front`` (mini-batches of 16, include/ttt_hip_lin_bwd_front.h): the side stream also runs, behind the recompute of a range, the
     half of its reverse steps that does not depend on the carried gradients (``ttt_linear_front_groups``, into one of two record
-    workspaces), and the caller's stream walks the range with ``ttt_linear_chain_groups`` instead of the sweep."""
+    workspaces), and the caller's stream walks the range with ``ttt_linear_chain_groups`` instead of the sweep.  At mini-batches of 64
+    ``front`` takes the entries of include/ttt_hip_lin64_bwd_front.h (``ttt_linear_front64_groups``, ``ttt_linear_chain64_groups``,
+    ``linear_backward_front64_records``) on the same schedule with the same arguments."""
     from ttt_amd.models.ssm.pipeline import part_ranges, run_in_parts
     (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, uW1, ub1, dOut, _, _, d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV) = tensors
     B, NH, NC, CS, F = XQ.shape
@@ -91,7 +100,11 @@ def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     dW1.copy_(uW1); db1.copy_(ub1)
     rec_args = (None, XK, XV, last_eta, ln_w, ln_b, W1c, b1c) + (None,) * 13
     if front:
-        records = space(ext.linear_backward_front_records(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl))
+        if CS == 64:
+            records_bytes, front_groups, chain_groups = ext.linear_backward_front64_records, ext.ttt_linear_front64_groups, ext.ttt_linear_chain64_groups
+        else:
+            records_bytes, front_groups, chain_groups = ext.linear_backward_front_records, ext.ttt_linear_front_groups, ext.ttt_linear_chain_groups
+        records = space(records_bytes(B, NH, NC, CS, F, G, ranges[0][1], XQ.dtype, impl=impl))
         front_args = (XQ, XK, XV, None, ln_w, ln_b, None, None, None, None, dOut) + (None,) * 7 + (dQ, None, None)
         walk_args = (XQ, XK, None, last_eta, ln_w, ln_b, None, None, dW1, db1, None, None, None, d_lnw, d_lnb, dW1, db1, d_eta, None, dK, dV)
     else:
@@ -100,11 +113,11 @@ def backward_in_parts(ext, impl, gpp, tensors, G, front=False):
     def side_work(n, p):
         ext.ttt_linear_recompute_groups(impl, *rec_args, G, *ranges[n], slots[p])
         if front:
-            ext.ttt_linear_front_groups(impl, *front_args, G, *ranges[n], slots[p], records[p])
+            front_groups(impl, *front_args, G, *ranges[n], slots[p], records[p])
 
     def main_work(n, p):
         if front:
-            ext.ttt_linear_chain_groups(impl, *walk_args, G, *ranges[n], slots[p], records[p], carry)
+            chain_groups(impl, *walk_args, G, *ranges[n], slots[p], records[p], carry)
         else:
             ext.ttt_linear_sweep_groups(impl, *walk_args, G, *ranges[n], slots[p], carry)
 
@@ -128,6 +141,12 @@ class HipLinear(torch.autograd.Function):
     # other call is what it is without it.  Same bits either way.  Default from the environment variable TTT_LINEAR_BACKWARD_FRONT, read
     # once at import.
     backward_front = _backward_front_default()
+    # The same at mini-batches of 64 (``ttt_linear_front64_groups`` / ``ttt_linear_chain64_groups``, csrc/ttt_lin64_body.h): 0 (default) or
+    # 1.  Read only where ``backward_parts`` selects the in-parts path at mini-batches of 64 with ``cs64_impl == "mfma"`` and the
+    # extension has the entries; ``backward_front`` keeps meaning mini-batches of 16 only.  Same bits either way.  The record
+    # workspaces are large (two of B * NH * backward_parts * G * 77 824 bytes).  Default from the environment variable
+    # TTT_LINEAR_BACKWARD_FRONT64, read once at import.
+    backward_front64 = _backward_front64_default()
     # The forward scan at mini-batches of 16 with its output path on a second wave (csrc/ttt_lin16_split_body.h): 0 (default) = the
     # one-wave scan, 1 = the two-wave form - in one piece here and in the parts of pipeline.py (the chunk picker of
     # ``pipeline.LINEAR_SCAN``) - where the call is bf16, head dim 64, mini-batches of 16, resolves to the MFMA scan and the extension
@@ -154,10 +173,15 @@ class HipLinear(torch.autograd.Function):
         return ext.resolved_impl(B, NH, NC, CS, F, G, XQ.dtype, mlp=False, backward=True, impl=impl) == "mfma"
 
     @staticmethod
-    def _with_front(ext, XQ):
+    def _with_front(ext, XQ, impl=None):
         v = HipLinear.backward_front
         if v not in (0, 1) or isinstance(v, bool):
             raise ValueError(f"HipLinear.backward_front: expected 0 or 1, got {v!r}")
+        if XQ.shape[3] == 64 and impl == "mfma" and hasattr(ext, "ttt_linear_chain64_groups"):
+            v64 = HipLinear.backward_front64
+            if v64 not in (0, 1) or isinstance(v64, bool):
+                raise ValueError(f"HipLinear.backward_front64: expected 0 or 1, got {v64!r}")
+            return v64 == 1
         return v == 1 and XQ.shape[3] == 16 and hasattr(ext, "ttt_linear_chain_groups")
 
     @staticmethod
@@ -211,7 +235,7 @@ class HipLinear(torch.autograd.Function):
         tensors = (XQ, XK, XV, last_eta, ln_w, ln_b, W1c, b1c, *up, grad_out.to(act).contiguous(), *grp,
                    d_lnw, d_lnb, dW1, db1, d_eta, dQ, dK, dV)
         if HipLinear._in_parts(ext, ctx.impl, XQ, G):
-            backward_in_parts(ext, ctx.impl, int(HipLinear.backward_parts), tensors, G, front=HipLinear._with_front(ext, XQ))
+            backward_in_parts(ext, ctx.impl, int(HipLinear.backward_parts), tensors, G, front=HipLinear._with_front(ext, XQ, ctx.impl))
         else:
             bwd = ext.ttt_linear_backward if ctx.impl is None else (lambda *a: ext.ttt_linear_backward_impl(ctx.impl, *a))
             bwd(*tensors, G)
